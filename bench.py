@@ -7,12 +7,18 @@ every cut instance of every fragment + the dense fp64 knit of the complete
 2^32-entry distribution (inputs = compiled plan, resident on the GPU).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload syc_32_5_p2] [--direct]
+                   [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
        or plain `python bench.py --gpus N`, which starts that launcher itself as a child process
        (WORLD_SIZE set and different from N is an error)
 
 value = reference-counted instances (sum over fragments of their label lists, run.py:37-39)
 processed per second by the whole job, timed between barriers, max over ranks.
+
+A plain run sets up, warms up, times the K steps and prints the line (config, roofline and sweep
+blocks from the timed steps' own events). --dump-outputs DIR writes what the last timed step returned.
+--full adds the legs that take runs of their own: npd, drop_in, knit_general, north_star_sweep,
+sweep_full, cpu_baseline (each with its --no-* switch).
 """
 import argparse
 import json
@@ -42,6 +48,14 @@ def parse():
                          "compression (K = 4^cuts; exact, same result)")
     ap.add_argument("--no-data-rank", action="store_true",
                     help="contract the light-cone terms as they are (no per-step data-rank compression)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own (one GPU): npd, "
+                         "drop_in, knit_general, north_star_sweep, sweep_full, cpu_baseline; the --no-* switches "
+                         "below leave single legs out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's array) as float64 DIR/<name>.npy: "
+                         "knit_out.npy if it has at most 2^22 entries, else knit_out_head.npy (its first 2^20 "
+                         "entries) and knit_out_sample.npy (2^22 entries at fixed seeded indices)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-north-star", action="store_true",
                     help="skip the syc 32 1 sweep-only measurement (north_star_sweep)")
@@ -445,6 +459,34 @@ def drop_in_timing(cut, ref_out, steps: int, device: int) -> dict:
             "virtual_circuit_ms": float(sum(builds) / len(builds)) * 1e3}
 
 
+DUMP_WHOLE, DUMP_HEAD, DUMP_SAMPLE, DUMP_SEED = 1 << 22, 1 << 20, 1 << 22, 20240611
+
+
+def dump_outputs(out, directory: str) -> dict:
+    """Write the array a step returned as float64 .npy files under ``directory`` (at most 40 MB): the
+    whole array when it has at most DUMP_WHOLE entries, else its first DUMP_HEAD entries and the
+    DUMP_SAMPLE entries at sorted indices drawn once from numpy's default_rng(DUMP_SEED), the same for
+    every run on an output of the same length. Returns {file name: entries}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    flat = out.reshape(-1)
+    n = flat.numel()
+    if n <= DUMP_WHOLE:
+        arrays = {"knit_out": flat}
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+        arrays = {"knit_out_head": flat[:DUMP_HEAD],
+                  "knit_out_sample": flat[torch.from_numpy(idx).to(flat.device)]}
+    written = {}
+    for name, a in arrays.items():
+        a = a.detach().to("cpu", torch.float64).contiguous().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name + ".npy"] = int(a.size)
+    return written
+
+
 def npd_timing(dense, accuracy: float) -> dict:
     """``QuasiDistr`` truncation + ``nearest_probability_distribution`` (quasi_distr.py:7-10,28-43,
     run.py:71) on the GPU over the step's 2^N output: qk_threshold_count then qk_npd, timed apart
@@ -725,12 +767,17 @@ def main():
     pipe.record_events = True
     pipe.events.clear()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        pipe.step()
+        last = pipe.step()
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0 and last is not None:
+        dumped = dump_outputs(last, args.dump_outputs)
+    del last
     if world > 1:
         import torch.distributed as dist
 
@@ -884,24 +931,27 @@ def main():
                              "full_knit_latency_ms: plain steps, one full knit each; roofline: the write launches of "
                              "the timed (pipelined) steps; sweep / rank_compress_ms: the plain steps (whole chip)")
         line["pipelined"] = pipelined
-    if world == 1 and not args.no_npd:
+    if dumped is not None:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "entries": dumped, "seed": DUMP_SEED}
+    full = args.full and world == 1  # the legs below take runs of their own
+    if full and not args.no_npd:
         from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import quasi_distr
 
         line["npd"] = npd_timing(pipe.out, quasi_distr.ACCURACY)
-    if world == 1 and not args.no_drop_in:
+    if full and not args.no_drop_in:
         line["drop_in"] = drop_in_timing(cut, pipe.out, args.steps, local)
         line["drop_in"]["vs_ms_per_step"] = line["drop_in"]["steady_ms"] / ms_per_step
     qs_host = None
-    if world == 1 and not args.no_cpu_baseline and pipe.dev_rank:
+    if full and not args.no_cpu_baseline and pipe.dev_rank:
         qs_host = [q.contiguous().cpu().numpy() for q in pipe.sweep()]
-    if world == 1 and not args.no_general and pipe.data_rank:
+    if full and not args.no_general and pipe.data_rank:
         line["knit_general"] = knit_general(dict(virt=virt, device=local, factored=not args.direct,
                                                  light_cone=not args.no_light_cone), max(2, args.steps // 4))
-    if world == 1 and not args.no_north_star:
+    if full and not args.no_north_star:
         line["north_star_sweep"] = north_star_sweep(args.steps)
-    if world == 1 and not args.no_sweep_full:
+    if full and not args.no_sweep_full:
         line["sweep_full"] = sweep_full(max(3, args.steps // 4))
-    if world == 1 and not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         if qs_host is not None:
             line["cpu_baseline"] = cpu_baseline_same(pipe, cut, qs_host)
             line["cpu_baseline"]["naive"] = cpu_baseline(cut, args.cpu_sample_labels)
