@@ -30,11 +30,12 @@ def matrix(name, params=()):
     p = [float(x) for x in params]
     r2 = 1 / math.sqrt(2)
     one = {
-        "id": lambda: np.eye(2), "x": lambda: np.array([[0, 1], [1, 0]]),
+        "id": lambda: np.eye(2), "i": lambda: np.eye(2), "x": lambda: np.array([[0, 1], [1, 0]]),
         "y": lambda: np.array([[0, -1j], [1j, 0]]), "z": lambda: np.diag([1, -1]),
         "h": lambda: np.array([[r2, r2], [r2, -r2]]), "s": lambda: _ph(math.pi / 2),
         "sdg": lambda: _ph(-math.pi / 2), "t": lambda: _ph(math.pi / 4), "tdg": lambda: _ph(-math.pi / 4),
         "sx": lambda: 0.5 * np.array([[1 + 1j, 1 - 1j], [1 - 1j, 1 + 1j]]),
+        "sxdg": lambda: 0.5 * np.array([[1 - 1j, 1 + 1j], [1 + 1j, 1 - 1j]]),  # conjugate transpose of sx
         "rx": lambda t: np.array([[math.cos(t / 2), -1j * math.sin(t / 2)], [-1j * math.sin(t / 2), math.cos(t / 2)]]),
         "ry": lambda t: np.array([[math.cos(t / 2), -math.sin(t / 2)], [math.sin(t / 2), math.cos(t / 2)]]),
         "rz": lambda t: np.diag([cmath.exp(-0.5j * t), cmath.exp(0.5j * t)]),
@@ -44,6 +45,11 @@ def matrix(name, params=()):
     }
     two = {
         "cx": lambda: _ctrl(np.array([[0, 1], [1, 0]])),
+        "cnot": lambda: _ctrl(np.array([[0, 1], [1, 0]])),  # qiskit's alias of cx
+        "ch": lambda: _ctrl(np.array([[r2, r2], [r2, -r2]])),
+        "crx": lambda t: _ctrl(one["rx"](t)),
+        "cry": lambda t: _ctrl(one["ry"](t)),
+        "cu1": lambda l: np.diag([1, 1, 1, cmath.exp(1j * l)]),  # the older name of cp
         "cy": lambda: _ctrl(np.array([[0, -1j], [1j, 0]])),
         "cz": lambda: np.diag([1, 1, 1, -1]),
         "cp": lambda l: np.diag([1, 1, 1, cmath.exp(1j * l)]),

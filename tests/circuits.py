@@ -3,7 +3,9 @@
 Each builder returns ``(uncut circuit, cut circuit)`` built with the
 package's circuit IR and cut-spec builder; they exercise every virtual-gate
 type of ``virtual_gates.py`` (CX/CZ/CY/RZZ generic + both degenerate angles/
-CPhase/Move), multi-cut labels, 2 and 3 fragments and traced qubits.
+CPhase/Move), multi-cut labels, 2 and 3 fragments and traced qubits. The gate-zoo
+builders (``gate_zoo``, ``gate_zoo_cut``, ``many_traced(zoo=True)``) draw from every
+gate of the package's table instead of ``u`` / ``cx`` alone.
 """
 import math
 import random
@@ -181,28 +183,168 @@ def same_fragment_cut(seed: int = 13):
     return qc, cut_circuit(qc, CutSpec([left, right], cut_idx))
 
 
-def many_traced(seed: int = 17, n0: int = 14, measured: tuple = (0, 5, 9)):
+def many_traced(seed: int = 17, n0: int = 14, measured: tuple = (0, 5, 9), zoo: bool = False):
     """A 14-qubit fragment that measures only 3 of its qubits (11 traced out: more than a SPLIT
     program's FINAL tile holds, engine._device_program widens and folds) joined by one CX cut to a
-    3-qubit fragment measured in full."""
+    3-qubit fragment measured in full. ``zoo``: the big fragment's ``u`` / ``cx`` body is replaced
+    by gate-zoo layers (every gate of the package's table, see :func:`gate_zoo`)."""
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.circuit import ClassicalRegister
     rng = random.Random(seed)
     n = n0 + 3
     qr = QuantumRegister(n, "q")
     cr = ClassicalRegister(len(measured) + 3, "c")
     qc = QuantumCircuit(qr, cr)
+    one, two = _zoo_deck(rng) if zoo else ([], [])
     _rand_layer(qc, range(n), rng)
-    for i in range(n0 - 1):
-        qc.cx(i, i + 1)
-    _rand_layer(qc, range(n0), rng)
+    if zoo:
+        _zoo_apply(qc, list(range(n0)), rng, one[::2], two[::2])
+    else:
+        for i in range(n0 - 1):
+            qc.cx(i, i + 1)
+        _rand_layer(qc, range(n0), rng)
     qc.cx(n0 - 1, n0)
     cut = [len(qc.data) - 1]
     qc.cx(n0, n0 + 1)
     qc.cx(n0 + 2, n0 + 1)
     _rand_layer(qc, range(n), rng)
-    for i in range(0, n0 - 1, 2):
-        qc.cx(i + 1, i)
-    _rand_layer(qc, range(n0), rng)
+    if zoo:
+        _zoo_apply(qc, list(range(n0)), rng, one[1::2], two[1::2])
+        _zoo_trailing(qc, list(range(n0)), rng)
+    else:
+        for i in range(0, n0 - 1, 2):
+            qc.cx(i + 1, i)
+        _rand_layer(qc, range(n0), rng)
     for c, q in enumerate(list(measured) + [n0, n0 + 1, n0 + 2]):
         qc.measure(q, c)
     return qc, cut_circuit(qc, CutSpec([list(range(n0)), list(range(n0, n))], cut))
+
+
+# ----------------------------------------------------------------------------- gate zoo
+_SPECIAL_ANGLES = (0.0, math.pi, math.pi / 2, -math.pi / 2, math.pi / 4)
+
+
+def _n_params(fn) -> int:
+    import inspect
+
+    return len(inspect.signature(fn).parameters)
+
+
+def _zoo_deck(rng):
+    """One seeded draw of every gate of the package's table: ``(one, two)`` lists of
+    ``(name, params)`` and ``(name, params, order)``. Every name appears with random parameters
+    (two-qubit names once per qubit order: ``order`` 0 puts ``qubits[0]`` — the control — on the
+    lower qubit index, 1 on the higher); every parametrised name also with special values: 0, pi
+    (``rx(pi)``: exact zeros on the diagonal), +-pi/2 (entries one ulp from 1/sqrt2) and pi/4; and
+    the Hadamard-type gates written as ``u`` / ``u2`` / ``r``. A few extra ``z`` / ``cz`` (real
+    diagonals: sign flips) so that some land on qubits outside a tile."""
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import gates
+
+    ang = lambda: rng.uniform(-math.pi, math.pi)  # noqa: E731
+    one, two = [], []
+    for name in sorted(gates.ONE_QUBIT):
+        k = _n_params(gates.ONE_QUBIT[name])
+        one.append((name, [ang() for _ in range(k)]))
+        if k:
+            for _ in range(2):
+                one.append((name, [rng.choice(_SPECIAL_ANGLES) for _ in range(k)]))
+    one += [("u", [math.pi / 2, 0.0, math.pi]), ("u2", [0.0, math.pi]), ("r", [math.pi, math.pi / 2]),
+            ("rx", [math.pi]), ("ry", [math.pi / 2]), ("z", []), ("z", []), ("x", [])]
+    for name in sorted(gates.TWO_QUBIT):
+        k = _n_params(gates.TWO_QUBIT[name])
+        for order in (0, 1):
+            two.append((name, [ang() for _ in range(k)], order))
+        if k:
+            for _ in range(2):
+                two.append((name, [rng.choice(_SPECIAL_ANGLES) for _ in range(k)], rng.randrange(2)))
+    two += [("cz", [], 0), ("cz", [], 1), ("cz", [], 0), ("crx", [math.pi], 1), ("cry", [math.pi / 2], 0)]
+    rng.shuffle(one)
+    rng.shuffle(two)
+    return one, two
+
+
+def _zoo_gate(qc, name, params, qubits):
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.circuit import Gate
+
+    qc.append(Gate(name, len(qubits), list(params)), list(qubits))
+
+
+def _zoo_apply(qc, qubits: list, rng, one: list, two: list):
+    """The deck's gates on ``qubits``: each two-qubit gate on a pair drawn from the whole list (so
+    that with a narrow tile one, both or neither of its qubits lies outside the tile), in the
+    order its deck entry asks for, with at most one one-qubit gate in front of it on each of its
+    qubits: one-qubit gates between two two-qubit gates are fused by the fragment compiler, and a
+    special matrix (exact zeros, +-1/sqrt2 entries) survives only where it stands alone. With a
+    single qubit only the one-qubit gates are applied."""
+    one = list(one)
+    if len(qubits) >= 2:
+        for name, params, order in two:
+            a, b = sorted(rng.sample(qubits, 2))
+            pair = (a, b) if order == 0 else (b, a)
+            for q in pair:
+                if one and rng.random() < 0.6:
+                    _zoo_gate(qc, *one.pop(), [q])
+            _zoo_gate(qc, name, params, pair)
+    for i, (name, params) in enumerate(one):
+        _zoo_gate(qc, name, params, [qubits[(7 * i + 3) % len(qubits)]])
+
+
+def _zoo_trailing(qc, qubits: list, rng):
+    """Trailing diagonal gates (``rz``, ``cp``, ``cz``, ``t``) on ``qubits``: unit phases nothing
+    non-diagonal follows, which sweep_plan.drop_trailing_phases removes from the program."""
+    for q in qubits:
+        if rng.random() < 0.5:
+            qc.rz(rng.uniform(-math.pi, math.pi), q)
+        else:
+            qc.t(q)
+    for k in range(min(4, len(qubits) // 2)):
+        a, b = rng.sample(qubits, 2)
+        if k % 2:
+            qc.cz(a, b)
+        else:
+            qc.cp(rng.uniform(-math.pi, math.pi), a, b)
+
+
+def gate_zoo(n: int, seed: int, unmeasured: tuple = ()):
+    """``(uncut circuit, the same circuit as ONE fragment: CutSpec([list(range(n))]))`` drawing from
+    every gate of the package's table (:func:`_zoo_deck`) on ``n`` qubits, ending in a layer of
+    diagonal gates on every qubit; the qubits of ``unmeasured`` are never measured (traced out)."""
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.circuit import ClassicalRegister
+    rng = random.Random(seed)
+    meas = [q for q in range(n) if q not in unmeasured]
+    qc = QuantumCircuit(QuantumRegister(n, "q"), ClassicalRegister(len(meas), "c"))
+    one, two = _zoo_deck(rng)
+    _zoo_apply(qc, list(range(n)), rng, one, two)
+    _zoo_trailing(qc, list(range(n)), rng)
+    for c, q in enumerate(meas):
+        qc.measure(q, c)
+    return qc, cut_circuit(qc, CutSpec([list(range(n))]))
+
+
+def gate_zoo_cut(seed: int, n0: int = 13, n1: int = 13, gate: str = "cx"):
+    """Two zoo fragments joined by one gate cut and one wire cut: qubits ``0..n0-1`` and
+    ``n0..n0+n1-1``, each with half of one zoo deck before the cuts and after them; a cut ``gate``
+    between the fragments; then qubit ``n0-1`` moves into fragment 1 (wire cut: that fragment gets a
+    carrier qubit, ``n1 + 1`` qubits in all) and goes on with fragment 1's qubits. The moved
+    qubit's place in fragment 0 and the last qubit of fragment 1 are never measured."""
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.circuit import ClassicalRegister
+    rng = random.Random(seed)
+    n = n0 + n1
+    w, skip = n0 - 1, n - 1
+    meas = [q for q in range(n) if q != skip]
+    qc = QuantumCircuit(QuantumRegister(n, "q"), ClassicalRegister(len(meas), "c"))
+    left, right = list(range(n0)), list(range(n0, n))
+    one, two = _zoo_deck(rng)
+    _zoo_apply(qc, left, rng, one[0::4], two[0::4])
+    _zoo_apply(qc, right, rng, one[1::4], two[1::4])
+    gate_cut = len(qc.data)
+    _zoo_gate(qc, gate, [rng.uniform(0.2, 2.9)] if gate in ("rzz", "cp") else [], [n0 - 2, n0 + 1])
+    wire_cut = len(qc.data)
+    _zoo_apply(qc, right + [w], rng, one[2::4], two[2::4])
+    _zoo_apply(qc, left[:-1], rng, one[3::4], two[3::4])
+    _zoo_trailing(qc, left[:-1], rng)
+    _zoo_trailing(qc, right + [w], rng)
+    for c, q in enumerate(meas):
+        qc.measure(q, c)
+    # the wire cut sits before the first instruction after the gate cut that touches w
+    first = next(i for i in range(wire_cut, len(qc.data)) if qc.qubits[w] in qc.data[i].qubits)
+    return qc, cut_circuit(qc, CutSpec([left, right], [gate_cut], [(first, w, 1)]))

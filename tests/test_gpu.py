@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import circuits
+import zoo_cases as zoo
 from oracle import dense, qvm
 
 from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
@@ -120,6 +121,7 @@ CASES = {
     "hwe_16_1_p3": lambda: cutting.config_cut_circuit("hwe", 16, 1, 3)[:2],
     "same_fragment": lambda: circuits.same_fragment_cut(),
     "many_traced": lambda: circuits.many_traced(),
+    "many_traced_zoo": lambda: circuits.many_traced(zoo=True),
 }
 
 
@@ -1843,3 +1845,179 @@ def test_syc_32_5_every_rank_slice_matches_reference_knit_samples(T):
                 del out, pipe
                 T.cuda.empty_cache()
             assert covered == len(keys_all)
+
+
+# ----------------------------------------------------------------------------- gate zoo
+# Seeded circuits over every gate of the package's table (circuits.gate_zoo, zoo_cases.py) on the
+# interpreter and the per-program kernels, against the oracle statevector. test_gate_zoo.py (CPU)
+# asserts that these programs at these widths reach every op kind, external-bit variant and special
+# path, and that their encodings are right.
+ZOO_SPLIT_IDS = [f"n{n}_tile{tb}" + (f"_final{ftb}" if ftb else "") for n, tb, ftb in zoo.SPLIT_RUNS]
+_ZOO_INTERP: dict = {}
+
+
+def _zoo_sweep(ctx, dprog, jobs):
+    slot_t, sign_t, _ = engine.jobs_to_device(jobs, 0)
+    return engine.sweep_jobs(ctx, dprog, slot_t, sign_t, jobs.n_jobs)[0]
+
+
+def _zoo_interpreter_row(T, n):
+    """The interpreter's row (qk_sweep, 12-bit tiles) of the uncut SPLIT zoo program, swept once."""
+    if n not in _ZOO_INTERP:
+        z = zoo.uncut(n)
+        dprog = engine.DeviceProgram.upload(z.prog, 0, jit=False)
+        assert dprog.module is None and not dprog.enc.packed and dprog.enc.tile_bits == zoo.INTERPRETER_TILE_BITS
+        _ZOO_INTERP[n] = _zoo_sweep(engine.get_context(0), dprog, z.jobs)
+        T.cuda.synchronize()
+    return _ZOO_INTERP[n]
+
+
+@pytest.mark.parametrize("n", sorted(zoo.SPLIT))
+def test_zoo_split_interpreter_matches_oracle(T, n):
+    """SPLIT zoo programs (13, 14 and 15 qubits; one and two of them traced out at 14 and 15) on
+    the interpreter kernel: every one of the 2^m outputs against the oracle."""
+    z = zoo.uncut(n)
+    got = _zoo_interpreter_row(T, n).cpu().numpy()
+    assert got.shape == (1, 1 << z.prog.m)
+    err = float(np.abs(got[0] - z.ref).max())
+    print(f"zoo n={n} interpreter: max|gpu - oracle| = {err:.3e}")
+    assert err <= TOL
+
+
+@pytest.mark.parametrize("n,tb,ftb", zoo.SPLIT_RUNS, ids=ZOO_SPLIT_IDS)
+def test_zoo_split_generated_kernels_match_oracle_and_interpreter(T, n, tb, ftb):
+    """The per-program kernels of the SPLIT zoo programs at every tile width below n (10-13 bits;
+    once with the FINAL tile narrowed to 10 bits): every output against the oracle (1e-12) and
+    against the interpreter's (1e-13); the fused label rows (qk_sweep_compiled_labels) against the
+    oracle and the reduced per-job rows."""
+    z = zoo.uncut(n)
+    ctx = engine.get_context(0)
+    dprog = engine.DeviceProgram.upload(z.prog, 0, jit=True, tile_bits=tb, final_tile_bits=ftb)
+    enc = dprog.enc
+    assert dprog.module is not None and not enc.packed and enc.tile_bits == tb
+    assert enc.pass_tile_bits(len(enc.passes) - 1) == (ftb or tb)
+    slot_t, sign_t, off_t = engine.jobs_to_device(z.jobs, 0)
+    got, _ = engine.sweep_jobs(ctx, dprog, slot_t, sign_t, 1)
+    fused, _ = engine.sweep_labels(ctx, dprog, slot_t, sign_t, 1, off_t, 1)
+    reduced = engine.reduce_labels(ctx, got, off_t, 1)
+    interp = _zoo_interpreter_row(T, n)
+    T.cuda.synchronize()
+    err = float(np.abs(got.cpu().numpy()[0] - z.ref).max())
+    err_fused = float(np.abs(fused.cpu().numpy()[0] - z.ref).max())
+    err_interp = float((got - interp).abs().max())
+    print(f"zoo n={n} tile {tb} final {ftb}: max|jit - oracle| = {err:.3e}, fused {err_fused:.3e}, "
+          f"max|jit - interpreter| = {err_interp:.3e}")
+    assert err <= TOL
+    assert err_fused <= TOL
+    assert err_interp <= 1e-13
+    assert T.allclose(fused, reduced, rtol=1e-14, atol=1e-18)
+
+
+def test_zoo_generated_kernels_take_lane_exchanges(T, monkeypatch):
+    """At least one zoo program's kernels hold a cross-lane exchange with QKNIT_SWEEP_LANE_XCHG=1
+    and none does with 0: the bit-identity test below compares different kernels."""
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import sweep_plan
+
+    encs = [sweep_plan.encode(zoo.uncut(n).prog, tile_bits=tb, final_tile_bits=ftb) for n, tb, ftb in zoo.SPLIT_RUNS]
+    monkeypatch.setenv("QKNIT_SWEEP_LANE_XCHG", "1")
+    assert sum(zoo.takes_lane_exchange(e) for e in encs) >= 1
+    monkeypatch.setenv("QKNIT_SWEEP_LANE_XCHG", "0")
+    assert not any(zoo.takes_lane_exchange(e) for e in encs)
+
+
+@pytest.mark.parametrize("n,tb,ftb", zoo.SPLIT_RUNS, ids=ZOO_SPLIT_IDS)
+def test_zoo_lane_exchange_sweep_is_bit_identical(T, monkeypatch, n, tb, ftb):
+    """The zoo programs' kernels with cross-lane exchanges (QKNIT_SWEEP_LANE_XCHG=1) against the
+    same programs through LDS only (0): the exchanges only move amplitudes between lanes, so the
+    rows are bit-identical."""
+    z = zoo.uncut(n)
+    ctx = engine.get_context(0)
+    rows = {}
+    for x in ("1", "0"):
+        monkeypatch.setenv("QKNIT_SWEEP_LANE_XCHG", x)
+        dprog = engine.DeviceProgram.upload(z.prog, 0, jit=True, tile_bits=tb, final_tile_bits=ftb)
+        assert dprog.module is not None
+        rows[x] = _zoo_sweep(ctx, dprog, z.jobs)
+    T.cuda.synchronize()
+    assert T.equal(rows["1"], rows["0"])
+
+
+@pytest.mark.parametrize("n", sorted(zoo.PACKED))
+def test_zoo_packed_interpreter_matches_oracle(T, n):
+    """PACKED zoo programs (n = 2 and 3: padded to 4 fiber bits; 6, 9; 12: a full tile) on the
+    interpreter, the one job repeated with different signs so that a tile holds several jobs, a
+    launch several tiles (n >= 3) and the last tile is partial: every row against the oracle."""
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.fragment_program import JobTable
+
+    z = zoo.uncut(n)
+    reps = zoo.PACKED_JOBS[n]
+    sign = np.array([1.0, -1.0, 0.5, -0.25])[np.arange(reps) % 4]  # exact scalings of the one distribution
+    jobs = JobTable(np.repeat(z.jobs.slot_mats, reps, axis=0), sign, np.arange(reps + 1, dtype=np.int64),
+                    np.zeros(reps, np.int64))
+    dprog = engine.DeviceProgram.upload(z.prog, 0)
+    enc = dprog.enc
+    assert enc.packed and dprog.module is None and enc.n_eff == max(n, 4)
+    assert reps >= 5 and (enc.jobs_per_tile == 1 or reps % enc.jobs_per_tile != 0)  # a partial last tile
+    got = _zoo_sweep(engine.get_context(0), dprog, jobs).cpu().numpy()
+    assert got.shape == (reps, 1 << z.prog.m)
+    err = float(np.abs(got - sign[:, None] * z.ref[None, :]).max())
+    print(f"zoo n={n} packed, {reps} jobs: max|gpu - oracle| = {err:.3e}")
+    assert err <= TOL
+
+
+def test_zoo_cut_fragment_rows_match_oracle(T):
+    """The cut zoo (13 + 14 qubits, one gate cut and one wire cut, a traced qubit in each fragment)
+    through prepare_fragments + sweep_fragment: about 6 labels per fragment — the first, the last,
+    ones with every slot non-trivial — against the oracle."""
+    zc = zoo.cut_zoo()
+    ctx = engine.get_context(0)
+    frags = engine.prepare_fragments(VirtualCircuit(zc.cut), 0)
+    assert [fs.prog.n for fs in frags] == [13, 14]
+    for fs, (frag, prog, labels) in zip(frags, zc.fragments()):
+        assert not fs.dprog.enc.packed and fs.prog.num_slots == 2 and fs.prog.n > fs.prog.m
+        assert fs.jobs.n_jobs > fs.n_rows and (fs.jobs.sign < 0).any()  # signed branch jobs
+        q = engine.sweep_fragment(ctx, fs).cpu().numpy()[fs.row_of_label()]
+        assert q.shape == (len(labels), 1 << prog.m)
+        for li in zc.picks(prog, labels):
+            assert tuple(fs.labels[li]) == tuple(labels[li])
+            err = float(np.abs(q[li] - zc.ref(frag, prog, labels[li])).max())
+            print(f"zoo cut n={prog.n} label {labels[li]}: max|gpu - oracle| = {err:.3e}")
+            assert err <= TOL
+
+
+def test_zoo_cut_multi_fragment_and_shared_init_sweeps_match_per_fragment(T, monkeypatch):
+    """The cut zoo's per-program kernels (slot ops, signed branch jobs summed per label, traced
+    qubits): the multi-fragment launch (QKNIT_SWEEP_MULTI=1) with shared INIT prefixes
+    (QKNIT_SWEEP_SHARE=1) and without (0) equals the per-fragment launches (QKNIT_SWEEP_MULTI=0)
+    bit for bit, and the picked labels' rows match the oracle."""
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.pipeline import KnitPipeline
+
+    zc = zoo.cut_zoo()
+
+    def sweep(multi, share):
+        monkeypatch.setenv("QKNIT_SWEEP_MULTI", multi)
+        monkeypatch.setenv("QKNIT_SWEEP_SHARE", share)
+        pipe = KnitPipeline(VirtualCircuit(zc.cut), factored=False, jit=True)
+        rows = [q.clone() for q in pipe.sweep()]
+        T.cuda.synchronize()
+        return pipe, rows
+
+    pipe0, ref = sweep("0", "1")
+    assert pipe0._multi is None and all(fs.dprog.module is not None for fs in pipe0.frags)
+    assert all(fs.jit == (True,) + zoo.CUT_JIT_BITS for fs in pipe0.frags)
+    pipe1, shared = sweep("1", "1")
+    assert pipe1._multi is not None and pipe1.be.shared_init == [7, None]  # 42 jobs start from 7 INIT tiles
+    pipe2, multi = sweep("1", "0")
+    assert pipe2._multi is not None and pipe2.be.shared_init == [None, None]
+    pipe3, plain = sweep("0", "0")
+    assert pipe3._multi is None
+    for rows in (shared, multi, plain):
+        assert len(rows) == len(ref) and all(T.equal(a, b) for a, b in zip(rows, ref))
+    for fs, q, (frag, prog, labels) in zip(pipe0.frags, ref, zc.fragments()):
+        q = q.cpu().numpy()
+        assert q.shape == (fs.n_rows, 1 << prog.m)
+        q = q[fs.row_of_label()]
+        for li in zc.picks(prog, labels):
+            err = float(np.abs(q[li] - zc.ref(frag, prog, labels[li])).max())
+            print(f"zoo cut jit n={prog.n} label {labels[li]}: max|gpu - oracle| = {err:.3e}")
+            assert err <= TOL
