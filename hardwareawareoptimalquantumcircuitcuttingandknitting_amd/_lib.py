@@ -143,6 +143,9 @@ SIGNATURES = {
     "qk_sample_cdf": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "qk_sample_counts": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_u64, c_vp]),
     "qk_fold_counts": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.c_double, c_vp]),
+    "qk_reduce_bits_workspace_bytes": (c_i32, [c_i64, ctypes.c_int, c_u64, c_i64, ctypes.POINTER(c_i64)]),
+    "qk_reduce_bits": (c_i32, [c_vp, c_i64, ctypes.c_int, c_vp, c_i64, c_u64, c_i64, ctypes.POINTER(c_u64), c_vp, c_i64,
+                               c_vp, c_i64]),
 }
 
 _lock = threading.Lock()

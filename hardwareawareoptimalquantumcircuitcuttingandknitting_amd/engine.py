@@ -645,6 +645,53 @@ def reduce_labels(ctx: Context, pjob, off_t, n_labels: int, q=None):
     return q
 
 
+REDUCE_BITS_BATCH = 16  # QK_REDUCE_BITS_BATCH: flip masks per launch (one read of the source each)
+
+
+def reduce_bits(ctx: Context, src, m: int, keep_mask: int, flips, out=None):
+    """``qk_reduce_bits``: ``out[r, j * 2^k + y] = sum over x < 2^m with pext(x, keep_mask) == y of
+    (-1)^popcount(x & flips[j]) * src[r, x]`` (k = popcount(keep_mask)) -> ``[rows, len(flips) * 2^k]``.
+    ``src``: float64 ``[rows, >= 2^m]`` with unit column stride (its row stride is ``ld_src``); it is
+    only read. ``flips``: Python ints below 2^m that do not overlap ``keep_mask``. ``out`` (optional):
+    a float64 tensor with unit column stride and at least that many columns; further ones stay as
+    they are."""
+    T = torch()
+    flips = [int(f) for f in flips]
+    m, keep_mask = int(m), int(keep_mask)
+    if not 0 <= m <= 30:
+        raise ValueError(f"m must be in 0..30, not {m}")
+    if keep_mask < 0 or keep_mask >> m:
+        raise ValueError(f"keep_mask {keep_mask:#x} outside the {m} bits")
+    if not flips:
+        raise ValueError("at least one flip mask (0 for a plain marginal)")
+    for f in flips:
+        if f < 0 or f >> m:
+            raise ValueError(f"flip mask {f:#x} outside the {m} bits")
+        if f & keep_mask:
+            raise ValueError(f"flip mask {f:#x} overlaps keep_mask {keep_mask:#x}")
+    if src.dim() != 2 or src.dtype != T.float64 or src.shape[1] < (1 << m) or (src.shape[1] > 1 and src.stride(1) != 1):
+        raise ValueError("src must be float64 [rows, >= 2^m] with unit column stride")
+    rows = src.shape[0]
+    ld_src = src.stride(0) if rows > 1 else max(src.stride(0), 1 << m)
+    width = len(flips) << bin(keep_mask).count("1")
+    if out is None:
+        out = T.empty((rows, width), dtype=T.float64, device=src.device)
+    if out.dim() != 2 or out.dtype != T.float64 or out.shape[0] != rows or out.shape[1] < width or (
+            out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError("out must be float64 [rows, >= len(flips) * 2^k] with unit column stride")
+    ld_dst = out.stride(0) if rows > 1 else max(out.stride(0), width)
+    if rows == 0:
+        return out
+    need = ctypes.c_int64()
+    ctx.check(ctx.lib.qk_reduce_bits_workspace_bytes(rows, m, keep_mask, len(flips), ctypes.byref(need)),
+              "qk_reduce_bits_workspace_bytes")
+    work = T.empty(need.value // 8, dtype=T.float64, device=src.device) if need.value else None
+    masks = (ctypes.c_uint64 * len(flips))(*flips)
+    ctx.check(ctx.lib.qk_reduce_bits(ctx.handle, rows, m, src.data_ptr(), ld_src, keep_mask, len(flips), masks,
+                                     out.data_ptr(), ld_dst, _ptr(work), need.value), "qk_reduce_bits")
+    return out
+
+
 # ----------------------------------------------------------------------------- shot sampling
 _SEED_STRIDE = 0x632BE59BD9B4E019  # per-fragment stream offset (mirrored by oracle/sampling.py)
 _U64 = (1 << 64) - 1

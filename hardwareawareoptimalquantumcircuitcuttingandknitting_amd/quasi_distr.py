@@ -60,6 +60,33 @@ class QuasiDistr(dict):
             out[k] = v
         return out
 
+    # ---- reductions ------------------------------------------------------------
+    def marginal(self, clbits) -> "QuasiDistr":
+        """The distribution of ``clbits`` alone (bit ``i`` of a new key = ``clbits[i]``), every other
+        bit summed out; truncated like every ``QuasiDistr``. Duplicate clbits raise ``ValueError``."""
+        cl = [int(c) for c in clbits]
+        if len(set(cl)) != len(cl) or any(c < 0 for c in cl):
+            raise ValueError(f"clbits must be distinct and non-negative: {cl}")
+        out: dict = {}
+        for key, v in self.items():
+            y = 0
+            for i, c in enumerate(cl):
+                y |= (key >> c & 1) << i
+            out[y] = out.get(y, 0.0) + v
+        return QuasiDistr(out)
+
+    def expectation(self, mask) -> float:
+        """``sum_key (-1)^popcount(key & mask) * value``: the expectation value of the Pauli-Z string
+        ``mask`` (an int, bit ``i`` = Z on clbit ``i``, or an ``'IZ'`` string, rightmost = clbit 0)."""
+        if isinstance(mask, str):
+            if set(mask.upper()) - set("IZ"):
+                raise ValueError(f"observable {mask!r}: only I and Z")
+            mask = sum(1 << i for i, ch in enumerate(reversed(mask.upper())) if ch == "Z")
+        mask = int(mask)
+        if mask < 0:
+            raise ValueError("mask must be non-negative")
+        return float(sum(-v if bin(k & mask).count("1") & 1 else v for k, v in self.items()))
+
     # ---- projection ------------------------------------------------------------
     def nearest_probability_distribution(self) -> dict:
         """Simplex projection of ``quasi_distr.py:28-43``.

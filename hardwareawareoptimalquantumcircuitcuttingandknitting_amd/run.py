@@ -493,3 +493,62 @@ def run_virtual_circuit(virt: VirtualCircuit, shots: int = 20000, *, device: int
         return out, info
     keys, vals = engine.nearest_probability_distribution(engine.get_context(device), out, _qd.ACCURACY)
     return dict(zip(keys.tolist(), vals.tolist())), info
+
+
+# ---------------------------------------------------------------------------- reductions of the knit
+def _reducer(virt: VirtualCircuit, device: int, factored, group, sample: bool):
+    """Sweep for the marginal / expectation entry points: ``(KnitReducer, run_time)``."""
+    from .observables import KnitReducer
+
+    if group is not None:
+        raise ValueError("marginals and expectation values run on one GPU (group must be None)")
+    if sample:
+        raise ValueError("marginals and expectation values are of the exact knit (sample=True is not supported)")
+    if not all(isinstance(virt.get_backend(f), MI355XBackend) for f in virt.fragment_circuits if len(f)):
+        raise ValueError("marginals and expectation values need every fragment on the MI355X backend")
+    log.info("Running virtualizer with %d %s fragments and %d vgates...", len(virt.fragment_circuits),
+             tuple(len(f) for f in virt.fragment_circuits), len(virt.vgate_instructions))
+    now = perf_counter()
+    red = KnitReducer(virt, device=device, factored=factored)
+    _sync(device)
+    return red, perf_counter() - now
+
+
+def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 0, dense: bool = False,
+                                 factored: bool | None = None, group=None, sample: bool = False):
+    """The knit's distribution of the clbits ``clbits`` alone (bit ``i`` of a key = ``clbits[i]``), all
+    others summed out, without the 2^N output: the swept rows are reduced per fragment
+    (``qk_reduce_bits``) and knitted narrow (:class:`observables.KnitReducer`). Returns
+    ``(result, RunTimeInfo)``; the sweep is ``run_time``, reduce + combine ``knit_time``.
+
+    ``dense=True``: the exact marginal as a float64 device tensor ``[2^k]``, not projected.
+    ``dense=False``: its ``ACCURACY`` truncation and ``nearest_probability_distribution`` as a dict, the
+    shape of :func:`run_virtual_circuit`'s result. Note that the projection does not commute with
+    summing: the NPD of a marginal is not the marginal of the NPD of the full distribution.
+
+    One GPU, exact instances, every fragment on the MI355X backend (``ValueError`` otherwise)."""
+    red, run_time = _reducer(virt, device, factored, group, sample)
+    now = perf_counter()
+    out = red.marginal(clbits)
+    if dense:
+        _sync(device)
+        return out, RunTimeInfo(run_time, perf_counter() - now)
+    keys, vals = engine.nearest_probability_distribution(red.ctx, out, _qd.ACCURACY)
+    info = RunTimeInfo(run_time, perf_counter() - now)
+    log.info("Knitted in %.2fs.", info.knit_time)
+    return dict(zip(keys.tolist(), vals.tolist())), info
+
+
+def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device: int = 0,
+                                    factored: bool | None = None, group=None, sample: bool = False):
+    """Expectation values of Pauli-Z strings on the exact knit (the quasi-distribution itself, no
+    projection): ``sum_key (-1)^popcount(key & mask) R[key]`` per observable, without the 2^N output.
+    ``observables``: int masks over the clbits, or ``'ZIIZ'`` strings (rightmost character = clbit 0,
+    one character per clbit). Returns ``(float64 [M], RunTimeInfo)``; the sweep is ``run_time``,
+    reduce + combine ``knit_time``. Same restrictions as :func:`run_virtual_circuit_marginal`."""
+    red, run_time = _reducer(virt, device, factored, group, sample)
+    now = perf_counter()
+    vals = red.expectation(observables)
+    info = RunTimeInfo(run_time, perf_counter() - now)
+    log.info("Knitted in %.2fs.", info.knit_time)
+    return vals, info

@@ -501,6 +501,25 @@ int qk_qd_merge(qk_ctx* ctx, int64_t na, const double* a, const int64_t* ka, int
 int qk_qd_axpby(qk_ctx* ctx, int64_t n, double alpha, const double* a, double beta, const double* b, double acc,
                 double* out);
 
+/* ---- bit reductions of swept rows (qknit_obs.hip): marginals and Z-string parities -----------
+ * dst[r * ld_dst + j * 2^k + y] = sum over x in [0, 2^m) with pext(x, keep_mask) == y of
+ *                                 (-1)^popcount(x & flip_masks[j]) * src[r * ld_src + x]
+ * for r < rows, j < n_flips, y < 2^k, k = popcount(keep_mask). A marginal is n_flips = 1 with flip 0;
+ * a batch of Z strings is keep_mask = 0 (one value per row and mask); k = m copies the rows bit for
+ * bit. 0 <= m <= 30; keep_mask and every flip mask below 2^m; flip_masks[j] & keep_mask == 0;
+ * ld_src >= 2^m; ld_dst >= n_flips * 2^k (columns beyond that are not written).
+ * src / dst / work are DEVICE pointers; flip_masks is a HOST array of n_flips masks, read before the
+ * call returns (the masks travel as kernel arguments, QK_REDUCE_BITS_BATCH per launch; the entry
+ * loops over the batches, so the source is read once per batch of masks, whatever their number).
+ * Deterministic: no atomics, every sum in an order fixed by (rows, m, keep_mask, n_flips); sums that
+ * span many tiles are split over workgroups and combined by a fixed-order second stage through
+ * `work` (qk_reduce_bits_workspace_bytes; 0 bytes for most shapes, then work may be NULL). */
+#define QK_REDUCE_BITS_BATCH 16
+int qk_reduce_bits_workspace_bytes(int64_t rows, int m, uint64_t keep_mask, int64_t n_flips, int64_t* bytes);
+int qk_reduce_bits(qk_ctx* ctx, int64_t rows, int m, const double* src, int64_t ld_src, uint64_t keep_mask,
+                   int64_t n_flips, const uint64_t* flip_masks, double* dst, int64_t ld_dst, void* work,
+                   int64_t work_bytes);
+
 int qk_hellinger(qk_ctx* ctx, int64_t n, const double* p, const double* q, double* acc3);
 
 #ifdef __cplusplus
