@@ -30,6 +30,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+from dataclasses import dataclass
 from time import perf_counter
 
 import numpy as np
@@ -232,8 +233,87 @@ def _joined(T, a, b):
     return T.cat([a.reshape(-1), b.reshape(-1)])
 
 
-class HipBackend:
+class Backend:
+    """What :class:`KnitPipeline` asks of the object that does its device work: the ``REQUIRED`` operations;
+    ``ROUTES``, operations whose presence changes the path a step takes (a backend lists those it has in
+    ``routes``, and the pipeline tests that set, never the attribute); ``OPTIONAL`` ones, called only where
+    a backend's own answers lead to them; and the methods below, which have a default. A subclass is checked
+    where it is defined: a missing operation or a public method the contract does not know (a misspelt one)
+    is a TypeError there instead of a quietly slower route later."""
+
+    REQUIRED = ("prepare_fragments", "upload_jobs", "workspace_bytes", "empty", "zeros", "to_device", "sweep",
+                "reduce_labels", "gather_rows", "gemm_keyed", "khatri_rao", "event")
+    ROUTES = {
+        "rank_factors": ("rank_factors", "compress", "probe_errors"),  # the device data rank (dev_rank)
+        "prep_operands": ("prep_operands",),  # its fused preparation (_fused_prep)
+        "sweep_rows": ("sweep_rows",),  # the plan's row pruning (_prune_rows)
+        "plan_multi": ("plan_multi", "sweep_multi"),  # one launch per pass round over all fragments
+        "knit_select": ("knit_select", "npd_pairs"),  # knit_dict without the 2^N vector
+        "out_buffer": ("out_buffer",),  # mapped, write-rate selected output buffers (new_out)
+        "knit_outer_stream": ("knit_outer_stream",),  # the streaming small-K write
+        "gemm_outer_paired": ("gemm_outer_paired",),  # the keyed small-K outer product
+    }
+    # with fuses_labels; with folded traced qubits; slice-mode / dense knit_dict
+    OPTIONAL = ("sweep_labels", "fold_traced", "probe_accept", "select_above", "npd_dense")
+    routes: frozenset = frozenset()
+    dev = None  # torch device; a "cuda" one means everything before the write is stream work (overlap_ok)
+    fuses_tally = False  # probe_errors(..., tally=) updates the data-rank statistics itself
+    shared_init = None  # per fragment of the last plan_multi: distinct shared INIT prefixes, or None
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        needs = cls.REQUIRED + tuple(op for r in cls.routes for op in cls.ROUTES[r])  # unknown route: KeyError
+        known = (set(cls.REQUIRED) | set(cls.OPTIONAL) | {op for ops in cls.ROUTES.values() for op in ops}
+                 | {n for n, v in vars(Backend).items() if callable(v)})  # ... and those with a default
+        bad = ([f"missing {n}" for n in needs if not callable(getattr(cls, n, None))]
+               + [f"{n} is not a Backend operation" for n, v in vars(cls).items()
+                  if callable(v) and not n.startswith("_") and n not in known])
+        if bad:
+            raise TypeError(f"{cls.__name__}: " + "; ".join(bad))
+
+    @staticmethod
+    def adopt(be):
+        """``be`` under the contract. An object of a class outside it (the earlier duck-typed interface) gets
+        a class of its own class and Backend: the defaults fill what it lacks, its routes are those whose
+        operations it defines — the one place where the presence of a method decides anything."""
+        if not isinstance(be, Backend):
+            kind = type(be)
+            routes = frozenset(r for r, ops in Backend.ROUTES.items()
+                               if all(callable(getattr(kind, op, None)) for op in ops))
+            be.__class__ = type(kind.__name__, (kind, Backend), {"routes": routes})
+        return be
+
+    def device_width(self, fs) -> int:
+        """Columns of the sweep's rows of fragment ``fs``."""
+        return 1 << fs.prog.m
+
+    def fuses_labels(self, fs) -> bool:
+        """Whether the sweep of ``fs`` can emit per-label rows itself (then ``sweep_labels``)."""
+        return False
+
+    def bind(self):
+        """Follow the caller's current stream (nothing to do on a host backend)."""
+
+    def outer_stream_kernel(self, K, clbits_a, clbits_b, nbits, o_begin=0, o_count=None) -> str:
+        """Name of the write kernel knit_outer_stream launches for these shapes."""
+        return type(self).__name__
+
+    def compress_v(self, TA, XA, TB, XB, probes, a_cols=None, a_width=None):
+        """(A2, B2, vpart): ``compress`` with the probe check's V pass fused in, or None (then the two apart)."""
+        return None
+
+    def rank_tally(self, r, k, acc):
+        """acc[0] += (r == 0), acc[1] += (r > 0 and k == 0), acc[2] = k, acc[3] += 1 (int64[4])."""
+        T = engine.torch()
+        rv, kv = int(r.reshape(-1)[0]), int(k.reshape(-1)[0])
+        acc += T.tensor([int(rv == 0), int(rv > 0 and kv == 0), 0, 1], dtype=T.int64)
+        acc[2] = kv
+
+
+class HipBackend(Backend):
     """Device work of the pipeline on one GPU through the C ABI."""
+
+    routes = frozenset(Backend.ROUTES)
 
     def __init__(self, device: int = 0):
         self.T = engine.torch()
@@ -277,8 +357,7 @@ class HipBackend:
         """Columns of the device sweep's rows (widened when traced qubits are folded afterwards)."""
         return 1 << (fs.dprog.enc.m if fs.dprog is not None else fs.prog.m)
 
-    def bind(self):
-        """Point the qk context at torch's current stream (a forked or a graph-capture stream)."""
+    def bind(self):  # torch's current stream may be a forked or a graph-capture stream
         self.ctx.bind_stream()
 
     def plan_multi(self, frags: list, sweeps: list):
@@ -320,8 +399,7 @@ class HipBackend:
         self.ctx.check(self.ctx.lib.qk_sweep_compiled_multi(self.ctx.handle, module, len(progs), progs, *rest),
                        "qk_sweep_compiled_multi")
 
-    def fuses_labels(self, fs) -> bool:
-        """Whether the sweep of ``fs`` can emit per-label rows itself (compiled program)."""
+    def fuses_labels(self, fs) -> bool:  # a compiled program's FINAL pass
         return fs.dprog is not None and fs.dprog.module is not None
 
     def sweep_labels(self, fs, slot, sign, n_jobs, off, n_labels, q, ws, chunks=None):
@@ -362,8 +440,7 @@ class HipBackend:
                                    tally=tally, vpart=vpart)
 
     def compress_v(self, TA, XA, TB, XB, probes, a_cols=None, a_width=None):
-        """(A2, B2, vpart): the compression with the probe check's V pass fused in, or None where
-        qk_compress_probe_v does not take the operands."""
+        """qk_compress_probe_v, or None where it does not take the operands."""
         if os.environ.get("QKNIT_COMPRESS_V", "1") == "0" or not engine.compress_probe_v_ok(XA, XB, a_cols):
             return None
         return engine.compress_probe_v(self.ctx, TA, XA, TB, XB, probes, a_cols=a_cols, a_width=a_width)
@@ -371,8 +448,7 @@ class HipBackend:
     def probe_accept(self, e2, r, tol, rel_tol=0.0):
         return engine.probe_accept(self.ctx, e2, r, tol, rel_tol)
 
-    def rank_tally(self, r, k, acc):
-        """acc[0] += (r == 0), acc[1] += (r > 0 and k == 0), acc[2] = k, acc[3] += 1 on the device."""
+    def rank_tally(self, r, k, acc):  # on the device
         self.ctx.check(self.ctx.lib.qk_rank_tally(self.ctx.handle, r.data_ptr(), k.data_ptr(), acc.data_ptr()),
                        "qk_rank_tally")
 
@@ -384,12 +460,6 @@ class HipBackend:
 
     def npd_pairs(self, keys, vals):
         return engine.npd_pairs(self.ctx, keys, vals)
-
-    def qprep_grams(self, WtA, qA, WtB, qB, probes):
-        return engine.qprep_grams(self.ctx, WtA, qA, WtB, qB, probes)
-
-    def qprep_compress_check(self, WtA, qA, WtB, qB, TA, TB, U, probes, r, tol, rel_tol):
-        return engine.qprep_compress_check(self.ctx, WtA, qA, WtB, qB, TA, TB, U, probes, r, tol, rel_tol)
 
     def select_above(self, dense, accuracy, key_base=0):
         return engine.select_above(self.ctx, dense, accuracy, key_base=key_base)
@@ -405,11 +475,27 @@ class HipBackend:
         return self.T.cuda.Event(enable_timing=True)
 
 
+@dataclass
+class PreparedStep:
+    """What the preparation of a device data-rank step (``_prep_dev_rank`` / ``_prep_slice``) hands to its
+    write (``_launch_dev_rank`` / ``_launch_slice``, ``knit_dict``)."""
+    A2: object  # compressed row-side operand [rmax, 2^mA]
+    B2: object  # compressed column-side operand [rmax, 2^mB]
+    k_eff: object  # device int32[1]: the accepted rank, 0 = rejected (the exact contraction runs)
+    mats: list  # per fragment: the exact operand X = Wt^T q (None for fragments outside the pair)
+    # finisher of the asynchronous exact gather -> (A, keyA, B, keyB): _prep_slice sets, _launch_slice calls it
+    exact: object = None
+    # QKNIT_SLICE_EXACT=host: (pinned copy of k_eff, its event or None); _prep_slice sets, _launch_slice waits
+    host_verdict: tuple | None = None
+    # the predicated exact slice is queued ahead of the write: _step_overlapped sets, _launch_slice reads
+    exact_queued: bool = False
+
+
 class KnitPipeline:
     def __init__(self, virt, device: int = 0, factored: bool = False, rank: int = 0, world: int = 1,
                  mode: str | None = None, group=None, backend=None, chunk_jobs: int | None = None,
                  jit: bool | None = None, light_cone: bool = True, data_rank: bool | None = None):
-        self.be = backend if backend is not None else HipBackend(device)
+        self.be = Backend.adopt(backend) if backend is not None else HipBackend(device)
         # branch jobs per sweep chunk of a fused (compiled) fragment; 0 = the whole fragment at once
         self.chunk_jobs = int(os.environ.get("QKNIT_SWEEP_CHUNK_JOBS", "0")) if chunk_jobs is None else chunk_jobs
         self.fork = False  # single mode: sweep each fragment on its own stream (set by capture_sweep)
@@ -482,10 +568,19 @@ class KnitPipeline:
         # device data rank (single / slice): qk_rank_factors + probe check + the predicated knits,
         # no host round trip before the write (single mode: none at all)
         self.dev_rank = bool(self.data_rank and cA is not None and self.ops.num_terms <= 64
-                             and hasattr(self.be, "rank_factors"))
+                             and "rank_factors" in self.be.routes)
         self._pending = 0  # device-rank steps whose statistics are not yet read back (sync_stats)
         self._tally = None  # device int64[4]: incompressible, rejected, last accepted rank, steps (_note_rank)
         self._tally_read = np.zeros(4, dtype=np.int64)
+        self._rank_rejects = 0  # host data rank: consecutive rejected compressions (RANK_GIVE_UP)
+        self._prune_mq = None  # while the plan prunes rows: per side, every swept row's largest entry
+        self._x_local = None  # sharded slice mode: this rank's column block of the fixed probes
+        self._exact_plan = None  # slice mode: per side, the columns and keys of this rank's exact slice
+        self._exact_stream = None  # sharded slice mode: helper stream reordering the gathered exact operands
+        self._started = []  # pipelined steps: events at the start of the last out_buffers steps
+        self._last_owner = None  # owner of the mapping new_out made last (None: a torch / backend tensor)
+        self._call_owner = None  # owner of the drop-in's output mapping, reused by later calls (take_out)
+        self._time_call_write = False  # the drop-in call's own write decides if that mapping stays
         # slice mode, fused preparation: every rank factors the same all-reduced Grams with the same
         # deterministic kernel, so no broadcast of the factors; each rank checks the rows of R in its
         # A column block against every probe, and a MIN all-reduce of the accepted ranks gives one
@@ -509,10 +604,6 @@ class KnitPipeline:
         # so the side stream's sweep waits for it), 6.55 with a one-workgroup-per-task write grid,
         # 6.06 with 4 write workgroups per CU. QKNIT_OVERLAP=1 turns it on.
         self.overlap = os.environ.get("QKNIT_OVERLAP", "0") == "1"
-        # speculative write (single-GPU device data rank): the probe check runs beside the write instead
-        # of before it (QKNIT_SPEC_WRITE=1)
-        self.spec_write = os.environ.get("QKNIT_SPEC_WRITE", "0") == "1"
-        self._spec_stream = None
         # pipelined steps: output buffers (QKNIT_OUT_BUFFERS; 2: steps alternate between two buffers and
         # two write streams, so step i+1's write may start while step i's drains). Default 2 at 4 ranks
         # only: rank_sim (modelled xGMI, 20 steps, 4 runs each) 1.56-1.64 vs 1.70-1.80 ms per step at 4
@@ -619,7 +710,7 @@ class KnitPipeline:
             n_local = len(sub.label_offsets) - 1
             slot_t, sign_t, off_t = be.upload_jobs(sub)
             n_jobs = sub.n_jobs
-            width = self.be.device_width(fs) if hasattr(self.be, "device_width") else 1 << fs.prog.m
+            width = be.device_width(fs)
             need = be.workspace_bytes(fs, n_jobs) if n_jobs else 0
             # gather / sharded slice mode: a rank's rows live in a zero-padded [per, width] buffer (the
             # unit of the collectives); padding rows stay zero
@@ -628,7 +719,7 @@ class KnitPipeline:
             alloc = be.zeros if sharded else be.empty
             branching = n_jobs != n_local
             # branching + compiled program: the FINAL pass writes the label rows (no pjob, no reduce)
-            fused = branching and n_jobs > 0 and getattr(be, "fuses_labels", lambda _: False)(fs)
+            fused = branching and n_jobs > 0 and be.fuses_labels(fs)
             chunks = None
             if fused and self.chunk_jobs and n_jobs > self.chunk_jobs:
                 offs = sub.label_offsets
@@ -658,7 +749,7 @@ class KnitPipeline:
         W = self.ops.transforms
         live = [i for i, fs in enumerate(self.frags) if not fs.dropped]
         if (self.row_prune <= 0 or len(live) != 2 or any(W[i] is None or not self.frags[i].jobs.n_jobs for i in live)
-                or not hasattr(self.be, "sweep_rows")):
+                or "sweep_rows" not in self.be.routes):
             return {}
         cms = {i: np.abs(np.asarray(W[i])).max(axis=0) for i in live}  # per swept row: largest entry
         qs, thr = None, self.row_prune
@@ -666,16 +757,16 @@ class KnitPipeline:
             keep = {i: np.flatnonzero(cms[i] > thr * cms[i].max()) for i in live}
             pruned = {i: k for i, k in keep.items() if k.size < cms[i].size}
             if not pruned:  # nothing below this threshold, so nothing below any smaller one
-                return {}
+                break
             if qs is None:
                 qs = {i: self.be.sweep_rows(self.frags[i]) for i in live}
             bound = self._prune_bound(qs, keep)
             if bound <= PRUNE_TOL:
                 self.prune_bound = bound
-                del self._prune_mq
+                self._prune_mq = None
                 return pruned
             thr /= 10
-        self.__dict__.pop("_prune_mq", None)
+        self._prune_mq = None
         return {}
 
     def _prune_bound(self, qs: dict, keep: dict) -> float:
@@ -686,7 +777,7 @@ class KnitPipeline:
         ``mq[j] = max_x |q[j, x]|`` the kept part of each operand row is bounded by the triangle
         inequality, ``max_x |X'_f[k, x]| <= sum_{j kept} |W_f[k, j]| mq[j]``, and
         ``d_f[k] = sum_{j pruned} |W_f[k, j]| mq[j]`` as before."""
-        if not hasattr(self, "_prune_mq"):
+        if self._prune_mq is None:
             self._prune_mq = {i: qs[i].abs().amax(dim=1).cpu().numpy() for i in sorted(keep)}
         m, d = [], []
         for i in sorted(keep):
@@ -766,9 +857,8 @@ class KnitPipeline:
         In gather mode the collectives then start after the one sweep (a rank's shard is small:
         one launch beats overlapping the row side's all_to_all with a second sweep)."""
         self._multi = None
-        if self.mode == "reduce" or os.environ.get("QKNIT_SWEEP_MULTI", "1") == "0":
-            return
-        if not hasattr(self.be, "plan_multi"):
+        if (self.mode == "reduce" or os.environ.get("QKNIT_SWEEP_MULTI", "1") == "0"
+                or "plan_multi" not in self.be.routes):
             return
         idx = [i for i, sw in enumerate(self.sweeps) if sw is not None]
         ok = all(self.sweeps[i]["n_jobs"] and self.sweeps[i]["chunks"] is None
@@ -983,12 +1073,12 @@ class KnitPipeline:
             self._probe = hit
         return self._probe
 
-    def _prep_step(self, qs) -> dict:
+    def _prep_step(self, qs) -> PreparedStep:
         """The device data-rank preparation of one step: the sharded slice collectives, or the local
         chain (single mode, replicated slice mode)."""
         return self._prep_slice(qs) if self.mode == "slice" and self.sharded else self._prep_dev_rank(qs)
 
-    def _launch_step(self, p: dict):
+    def _launch_step(self, p: PreparedStep):
         return self._launch_slice(p) if self.mode == "slice" else self._launch_dev_rank(p)
 
     def knit(self, qs: list):
@@ -1022,7 +1112,7 @@ class KnitPipeline:
             # not numerically low-rank to the tolerance: exact contraction for this step; compression is
             # given up only after RANK_GIVE_UP consecutive rejections (a borderline step does not turn
             # the fast path off for the pipeline's life)
-            self._rank_rejects = getattr(self, "_rank_rejects", 0) + 1
+            self._rank_rejects += 1
             if self._rank_rejects >= self.RANK_GIVE_UP:
                 self.data_rank = False
             self.rank_fallbacks += 1
@@ -1041,25 +1131,12 @@ class KnitPipeline:
         qk_rank_factors -> qk_compress_operands -> qk_probe_errors): factored transforms on both sides, a backend
         with those kernels, and operand shapes they take."""
         ia, ib = self.order[0], self.order[-1]
-        if not hasattr(self.be, "prep_operands") or self.transforms[ia] is None or self.transforms[ib] is None:
+        if "prep_operands" not in self.be.routes or self.transforms[ia] is None or self.transforms[ib] is None:
             return False
         K = self.transforms[ia].shape[1]
         return (self.transforms[ib].shape[1] == K and self.transforms[ia].shape[0] == qs[ia].shape[0]
                 and self.transforms[ib].shape[0] == qs[ib].shape[0]
                 and engine.prep_ok(K, qs[ia].shape[1], qs[ib].shape[1]))
-
-    def _qspace_prep(self, qs) -> bool:
-        """Whether the data-rank step takes the q-space chain (qk_qprep_grams -> qk_rank_factors ->
-        qk_qprep_compress_check; engine.qprep_ok shapes: at most 80 swept rows per side): a backend with
-        those entries, factored transforms on both sides, no speculative write (it checks beside the write
-        on the X path's operands)."""
-        ia, ib = self.order[0], self.order[-1]
-        if self.spec_write or not hasattr(self.be, "qprep_grams") or self.transforms[ia] is None \
-                or self.transforms[ib] is None:
-            return False
-        WA, WB = self.transforms[ia], self.transforms[ib]
-        return (WA.shape[1] == WB.shape[1] and WA.shape[0] == qs[ia].shape[0] and WB.shape[0] == qs[ib].shape[0]
-                and engine.qprep_ok(WA.shape[1], WA.shape[0], WB.shape[0], qs[ia].shape[1], qs[ib].shape[1]))
 
     def _prep_fused(self, qs, probes):
         """(mats, G, U): light-cone operands of the two sides, their Grams [2, K, K] and the B side
@@ -1091,66 +1168,18 @@ class KnitPipeline:
             self._note_rank(r, k_eff)
         return k_eff, err
 
-    def _prep_dev_rank(self, qs) -> dict:
+    def _prep_dev_rank(self, qs) -> PreparedStep:
         """Single GPU, device data rank: operands + Grams + probe products (one fused launch where
         the shapes allow, else the transforms and torch products), qk_rank_factors with its
         acceptance check, compressed operands. Nothing waits for the host; ``sync_stats`` reads
         ranks / fallbacks later. The write (``_launch_dev_rank``) runs with the accepted rank and
         the exact contraction is predicated on it being 0."""
         ia, ib = self.order[0], self.order[-1]
-        if self._qspace_prep(qs):
-            # q-space chain (DESIGN §2): Grams and probe products from q q^T / q P^T, the compressed operands
-            # from (T Wt^T) q; X = Wt^T q is formed only by the predicated transforms of the exact path
-            T = self.T
-            x = self._probes(qs[ib].shape[1], qs[ib].device)
-            WA, WB = self.transforms[ia], self.transforms[ib]
-            qA, qB = qs[ia].contiguous(), qs[ib].contiguous()
-            G, U = self.be.qprep_grams(WA, qA, WB, qB, x)
-            TA, TB, r = self.be.rank_factors(G[0], G[1])
-            A2, B2, k_eff, _ = self.be.qprep_compress_check(WA, qA, WB, qB, TA, TB, U, x, r, self.rank_tol,
-                                                            self.rank_tol_rel)
-            self._note_rank(r, k_eff)
-            mats = [None] * len(qs)
-            for i, W, q in ((ia, WA, qA), (ib, WB, qB)):  # written only when the check rejected (k = 0)
-                mats[i] = T.empty((W.shape[1], q.shape[1]), dtype=T.float64, device=q.device)
-                self.be.gemm_keyed(W, q, out=mats[i], strideA=q.shape[1], skip=k_eff)
-            self.last_prep = "qspace"
-            return {"A2": A2, "B2": B2, "k_eff": k_eff, "mats": mats}
         if self._fused_prep(qs):
             x = self._probes(qs[ib].shape[1], qs[ib].device)
             mats, G, U = self._prep_fused(qs, x)
             TA, TB, r = self.be.rank_factors(G[0], G[1])
-            if not self.spec_write:
-                return self._compress_and_check(TA, TB, r, mats, U, x)
-            A2, B2 = self.be.compress(TA, mats[ia], TB, mats[ib])
-            if self.spec_write and getattr(self.be, "dev", None) is not None and self.be.dev.type == "cuda":
-                # speculative write: the write runs at the factored rank r while the probe check runs
-                # beside it on a side stream; the exact contraction after both is predicated on the
-                # check (k = 0) and overwrites every output, as when the write was skipped
-                T = self.T
-                main = T.cuda.current_stream()
-                if self._spec_stream is None:
-                    self._spec_stream = T.cuda.Stream(device=self.be.dev)
-                S2 = self._spec_stream
-                S2.wait_stream(main)
-                with T.cuda.stream(S2):
-                    self.be.bind()
-                    _, k_eff, _ = self.be.probe_errors(mats[ia], A2, U, B2, x, r=r, tol=self.rank_tol,
-                                                       rel_tol=self.rank_tol_rel)
-                    self._note_rank(r, k_eff)
-                self.be.bind()
-                for t in (mats[ia], A2, U, B2, x, r, k_eff):
-                    t.record_stream(S2)
-                return {"A2": A2, "B2": B2, "k_eff": k_eff, "k_write": r, "check": S2, "mats": mats}
-            if getattr(self.be, "fuses_tally", False):  # the statistics in the accept kernel: one launch fewer
-                _, k_eff, _ = self.be.probe_errors(mats[ia], A2, U, B2, x, r=r, tol=self.rank_tol,
-                                                   rel_tol=self.rank_tol_rel, tally=self._tally_for(r.device))
-                self._pending += 1
-            else:
-                _, k_eff, _ = self.be.probe_errors(mats[ia], A2, U, B2, x, r=r, tol=self.rank_tol,
-                                                   rel_tol=self.rank_tol_rel)
-                self._note_rank(r, k_eff)
-            return {"A2": A2, "B2": B2, "k_eff": k_eff, "mats": mats}
+            return self._compress_and_check(TA, TB, r, mats, U, x)
         mats = self.operands(qs)
         self.last_prep = "torch"
         A, B = mats[ia], mats[ib]
@@ -1158,10 +1187,10 @@ class KnitPipeline:
         TA, TB, r = self.be.rank_factors(G[0].contiguous(), G[1].contiguous())
         A2, B2 = (TA @ A).contiguous(), (TB @ B).contiguous()
         k_eff, _ = self._accept(A, B, A2, B2, self._probes(B.shape[1], B.device), r)
-        return {"A2": A2, "B2": B2, "k_eff": k_eff, "mats": mats}
+        return PreparedStep(A2, B2, k_eff, mats)
 
-    def _compress_and_check(self, TA, TB, r, mats, U, x) -> dict:
-        """The fused chain's compression and probe check (no speculative write): the compressed operands
+    def _compress_and_check(self, TA, TB, r, mats, U, x) -> PreparedStep:
+        """The fused chain's compression and probe check: the compressed operands
         and the accepted rank of a prepared step. With the backend's fused form (compress_v) the check's V
         pass runs inside the compression. A replicated slice rank reads only A columns [base, base + n)
         (rows of R): it compresses those and checks those rows against every probe — its own slice's
@@ -1170,7 +1199,7 @@ class KnitPipeline:
         ia, ib = self.order[0], self.order[-1]
         a_cols = self._replicated_a_cols()
         kw = {"a_cols": a_cols} if a_cols is not None else {}
-        cv = self.be.compress_v(TA, mats[ia], TB, mats[ib], x, **kw) if hasattr(self.be, "compress_v") else None
+        cv = self.be.compress_v(TA, mats[ia], TB, mats[ib], x, **kw)
         check = {}
         if cv is not None:
             A2, B2, check["vpart"] = cv
@@ -1180,7 +1209,7 @@ class KnitPipeline:
         if a_cols is not None:
             XA = XA[:, a_cols[0]:a_cols[0] + a_cols[1]]
             check["a2_cols"] = a_cols
-        tally = getattr(self.be, "fuses_tally", False)  # the statistics in the accept kernel: one launch fewer
+        tally = self.be.fuses_tally  # the statistics in the accept kernel: one launch fewer
         if tally:
             check["tally"] = self._tally_for(r.device)
         _, k_eff, _ = self.be.probe_errors(XA, A2, U, B2, x, r=r, tol=self.rank_tol, rel_tol=self.rank_tol_rel,
@@ -1189,29 +1218,32 @@ class KnitPipeline:
             self._pending += 1
         else:
             self._note_rank(r, k_eff)
-        return {"A2": A2, "B2": B2, "k_eff": k_eff, "mats": mats}
+        return PreparedStep(A2, B2, k_eff, mats)
 
-    def _kernel_name(self, K, cA, cB, o_begin=0, o_count=None):
-        """The write kernel knit_outer_stream launches (the backend's answer; its class name otherwise)."""
-        name = getattr(self.be, "outer_stream_kernel", None)
-        return name(K, cA, cB, self.N, o_begin, o_count) if name else type(self.be).__name__
-
-    def _launch_dev_rank(self, p: dict):
+    def _launch_dev_rank(self, p: PreparedStep):
         ia, ib = self.order[0], self.order[-1]
         cA, cB = self.ops.clbits[ia], self.ops.clbits[ib]
         if self.record_events:
             start, end = self.be.event(), self.be.event()
             start.record()
-        self.last_kernel = self._kernel_name(p["A2"].shape[0], cA, cB)
-        self.be.knit_outer_stream(p["A2"], p["B2"], cA, cB, self.N, self.out, k_dev=p.get("k_write", p["k_eff"]))
+        self.last_kernel = self.be.outer_stream_kernel(p.A2.shape[0], cA, cB, self.N)
+        self.be.knit_outer_stream(p.A2, p.B2, cA, cB, self.N, self.out, k_dev=p.k_eff)
         if self.record_events:
             end.record()
             self.events.append((start, end))
-        if "check" in p:  # speculative write: the exact path waits for the probe check
-            self.T.cuda.current_stream().wait_stream(p["check"])
-        return self._contract(p["mats"], skip=p["k_eff"])  # exact path: runs only if the check rejected
+        return self._contract(p.mats, skip=p.k_eff)  # exact path: runs only if the check rejected
 
-    def _prep_slice(self, qs) -> dict:
+    def _broadcast_factors(self, TA, TB, r):
+        """(TA, TB, r) of the first rank on every rank of the group: one broadcast of the three packed."""
+        import torch.distributed as dist
+
+        T = self.T
+        R8, K = TA.shape
+        fac = T.cat([TA.reshape(-1), TB.reshape(-1), r.to(T.float64)])
+        dist.broadcast(fac, src=self._group_rank0(), group=self.group)
+        return fac[:R8 * K].view(R8, K), fac[R8 * K:2 * R8 * K].view(R8, K), fac[-1:].to(T.int32)
+
+    def _prep_slice(self, qs) -> PreparedStep:
         """Slice mode (multi-GPU), the preparation of this rank's write: ``qs`` hold every instance
         row of this rank's column block of each operand (the sweep's all_to_all). Collectives (fused
         preparation): one all_reduce of the two Grams + the B side against the probes, one
@@ -1227,11 +1259,12 @@ class KnitPipeline:
         ia, ib = self.order[0], self.order[-1]
         bwA, bwB = qs[ia].shape[1], qs[ib].shape[1]
         x_full = self._probes(bwB * P, qs[ib].device)  # [N_PROBES, wB]
-        if getattr(self, "_x_local", None) is None or self._x_local.shape[1] != bwB:  # fixed probes: once
+        if self._x_local is None or self._x_local.shape[1] != bwB:  # fixed probes: once
             self._x_local = x_full[:, self.rank * bwB:(self.rank + 1) * bwB].contiguous()
         x = self._x_local
         npr = self.N_PROBES
-        if self._fused_prep(qs):
+        fused = self._fused_prep(qs)
+        if fused:
             mats, G, U = self._prep_fused(qs, x)
             XA, XB = mats[ia], mats[ib]
             K = XA.shape[0]
@@ -1240,13 +1273,8 @@ class KnitPipeline:
             G = red[:2 * K * K].view(2, K, K)
             U = red[2 * K * K:].view(K, npr).contiguous()
             TA, TB, r = be.rank_factors(G[0].contiguous(), G[1].contiguous())
-            R8 = TA.shape[0]
             if self.slice_sync:
-                fac = T.cat([TA.reshape(-1), TB.reshape(-1), r.to(T.float64)])
-                dist.broadcast(fac, src=self._group_rank0(), group=self.group)
-                TA = fac[:R8 * K].view(R8, K)
-                TB = fac[R8 * K:2 * R8 * K].view(R8, K)
-                r = fac[-1:].to(T.int32)
+                TA, TB, r = self._broadcast_factors(TA, TB, r)
             A2l, B2l = be.compress(TA.contiguous(), XA, TB.contiguous(), XB)
             loc = _joined(T, A2l, B2l)
         else:
@@ -1259,20 +1287,15 @@ class KnitPipeline:
             GA = red[:K * K].view(K, K).contiguous()
             GB = red[K * K:2 * K * K].view(K, K).contiguous()
             Bx = red[2 * K * K:].view(K, npr)
-            TA, TB, r = be.rank_factors(GA, GB)
-            R8 = TA.shape[0]
-            fac = T.cat([TA.reshape(-1), TB.reshape(-1), r.to(T.float64)])
-            dist.broadcast(fac, src=self._group_rank0(), group=self.group)
-            TA = fac[:R8 * K].view(R8, K)
-            TB = fac[R8 * K:2 * R8 * K].view(R8, K)
-            r = fac[-1:].to(T.int32)
+            TA, TB, r = self._broadcast_factors(*be.rank_factors(GA, GB))
             loc = T.cat([(TA @ XA).reshape(-1), (TB @ XB).reshape(-1)])
+        R8 = TA.shape[0]
         gat = T.empty(P * loc.numel(), dtype=loc.dtype, device=loc.device)
         dist.all_gather_into_tensor(gat, loc, group=self.group)
         gat = gat.view(P, loc.numel())
         A2 = gat[:, :R8 * bwA].view(P, R8, bwA).permute(1, 0, 2).reshape(R8, P * bwA).contiguous()
         B2 = gat[:, R8 * bwA:].view(P, R8, bwB).permute(1, 0, 2).reshape(R8, P * bwB).contiguous()
-        if self._fused_prep(qs):
+        if fused:
             # this rank's A columns (its rows of R) against all probes (B2 / probes: every column)
             # (the accepted rank from the same launch chain: no separate accept kernel)
             _, k_eff, _ = be.probe_errors(XA, A2, U, B2, x_full.contiguous(), r=r, tol=self.rank_tol,
@@ -1296,15 +1319,13 @@ class KnitPipeline:
             ready = T.cuda.Event() if on_gpu else None
             if on_gpu:
                 ready.record()
-            return {"A2": A2, "B2": B2, "k_eff": k_eff, "XA": XA, "XB": XB, "pinned": pinned, "ready": ready,
-                    "mats": mats}
+            return PreparedStep(A2, B2, k_eff, mats, host_verdict=(pinned, ready))
         # the exact slice's operands, gathered every step (the same collectives on every rank whatever
         # the verdict; the contraction itself is predicated on the device, _launch_slice); started
         # asynchronously, so the write does not wait for them — only the predicated contraction does
-        ex = self._slice_exact_operands(XA, XB, async_op=True)
-        return {"A2": A2, "B2": B2, "k_eff": k_eff, "exact": ex, "mats": mats}
+        return PreparedStep(A2, B2, k_eff, mats, exact=self._slice_exact_operands(XA, XB, async_op=True))
 
-    def _launch_slice(self, p: dict):
+    def _launch_slice(self, p: PreparedStep):
         be = self.be
         ia, ib = self.order[0], self.order[-1]
         cA, cB = self.ops.clbits[ia], self.ops.clbits[ib]
@@ -1312,9 +1333,8 @@ class KnitPipeline:
         if self.record_events:
             start, end = be.event(), be.event()
             start.record()
-        self.last_kernel = self._kernel_name(p["A2"].shape[0], cA, cB, o_begin, o_count)
-        be.knit_outer_stream(p["A2"], p["B2"], cA, cB, self.N, self.out, o_begin=o_begin, o_count=o_count,
-                             k_dev=p["k_eff"])
+        self.last_kernel = be.outer_stream_kernel(p.A2.shape[0], cA, cB, self.N, o_begin, o_count)
+        be.knit_outer_stream(p.A2, p.B2, cA, cB, self.N, self.out, o_begin=o_begin, o_count=o_count, k_dev=p.k_eff)
         if self.record_events:
             end.record()
             self.events.append((start, end))
@@ -1322,28 +1342,29 @@ class KnitPipeline:
             # replicated preparation: every rank holds the whole transformed operands, so the exact
             # slice (predicated on this rank's own verdict over its slice's rows) reads its columns in
             # place — no collective. Pipelined steps queue it before the write (_step_overlapped)
-            if p.get("exact_queued"):
+            if p.exact_queued:
                 return self.out
             A, kA, B, kB = self._slice_exact_operands(*self._exact_mats(p))
-            be.gemm_keyed(A, B, keyA=kA, keyB=kB, out=self.out, skip=p["k_eff"])
+            be.gemm_keyed(A, B, keyA=kA, keyB=kB, out=self.out, skip=p.k_eff)
             return self.out
-        if "exact" not in p:  # slice_exact == "host"
-            if p["ready"] is not None:
-                p["ready"].synchronize()  # the check only, not the knit queued behind it
-            if int(p["pinned"][0]) == 0:
-                self._slice_exact(p["XA"], p["XB"], cA, cB)
+        if p.host_verdict is not None:  # slice_exact == "host"
+            pinned, ready = p.host_verdict
+            if ready is not None:
+                ready.synchronize()  # the check only, not the knit queued behind it
+            if int(pinned[0]) == 0:
+                self._slice_exact(*self._exact_mats(p), cA, cB)
             return self.out
         # exact contraction of this slice, predicated on the device: runs only when the (MIN-reduced)
         # accepted rank is 0 — no host round trip, the verdict is read later by sync_stats
-        A, kA, B, kB = p["exact"]()
-        be.gemm_keyed(A, B, keyA=kA, keyB=kB, out=self.out, skip=p["k_eff"])
+        A, kA, B, kB = p.exact()
+        be.gemm_keyed(A, B, keyA=kA, keyB=kB, out=self.out, skip=p.k_eff)
         return self.out
 
     # ------------------------------------------------------------------ overlapped steps
     def overlap_ok(self) -> bool:
         """Whether steps can be software-pipelined (``step(overlap=True)``): the device data-rank
         path (single or slice mode) on a GPU backend, so everything before the write is stream work."""
-        return bool(self.dev_rank and self.mode in ("single", "slice") and getattr(self.be, "dev", None) is not None
+        return bool(self.dev_rank and self.mode in ("single", "slice") and self.be.dev is not None
                     and self.be.dev.type == "cuda")
 
     # CUs of the preparation stream in a pipelined step (QKNIT_PREP_CUS; 0: no CU split). rank_sim, 8
@@ -1388,15 +1409,8 @@ class KnitPipeline:
                 self._write_stream = engine.cu_masked_stream(dev, write)
                 self._write_cus = write
                 self.overlap_cus = (len(prep), len(write))
-            else:
-                # QKNIT_OVERLAP_PRIO: HSA queue priorities instead of a CU split. "write": the write
-                # stream high, the preparation normal (the dispatcher serves the preparation's
-                # workgroups only where the write's queue has none left: its tail); "prep": the
-                # preparation high (its few workgroups go first, the write keeps every CU)
-                prio = os.environ.get("QKNIT_OVERLAP_PRIO", "")
-                hi = min(T.cuda.Stream.priority_range()) if prio else 0
-                self._prep_stream = T.cuda.Stream(device=self.be.dev, priority=hi if prio == "prep" else 0)
-                self._write_stream = T.cuda.Stream(device=self.be.dev, priority=hi) if prio == "write" else None
+            else:  # no CU split: a plain side stream for the preparation, the write on the caller's stream
+                self._prep_stream = T.cuda.Stream(device=self.be.dev)
                 self.overlap_cus = (0, total)
             self._prep_stream.wait_stream(T.cuda.current_stream())  # plan uploads before the first step
         return self._prep_stream, self._write_stream
@@ -1428,7 +1442,7 @@ class KnitPipeline:
         # write may still start under step j - 1's)
         started = T.cuda.Event()
         started.record(main)
-        self._started = (getattr(self, "_started", []) + [started])[-max(self.out_buffers, 1):]
+        self._started = (self._started + [started])[-max(self.out_buffers, 1):]
         if self.out_buffers > 1:
             nb = self.out_buffers
             self._ensure_outs(W, main)
@@ -1456,8 +1470,8 @@ class KnitPipeline:
                 if len(self._started) == max(self.out_buffers, 1):
                     S.wait_event(self._started[0])
                 A, kA, B, kB = self._slice_exact_operands(*self._exact_mats(p))
-                be.gemm_keyed(A, B, keyA=kA, keyB=kB, out=self.out, skip=p["k_eff"])
-                p["exact_queued"] = True
+                be.gemm_keyed(A, B, keyA=kA, keyB=kB, out=self.out, skip=p.k_eff)
+                p.exact_queued = True
             done = T.cuda.Event(enable_timing=self.record_events)
             done.record(S)
         if self.record_events:
@@ -1467,11 +1481,9 @@ class KnitPipeline:
             if W is not main and len(self._started) == max(self.out_buffers, 1):
                 W.wait_event(self._started[0])
             be.bind()
-            for k in ("A2", "B2", "k_eff"):
-                p[k].record_stream(W)
-            for m in p["mats"]:
-                if m is not None:
-                    m.record_stream(W)
+            for t in (p.A2, p.B2, p.k_eff, *p.mats):
+                if t is not None:
+                    t.record_stream(W)
             out = self._launch_step(p)
         if W is not main:
             main.wait_stream(W)
@@ -1480,9 +1492,9 @@ class KnitPipeline:
 
     def _replicated_a_cols(self):
         """(base, n): the A columns this rank's output slice reads in replicated slice mode, when that is
-        fewer than all of them (syc 32 5 at 8 ranks: 2^13 of 2^16) and the speculative write is off;
-        else None. QKNIT_SLICE_A_COLS=0 compresses and checks all columns (A/B)."""
-        if self.mode != "slice" or self.sharded or self.spec_write or os.environ.get("QKNIT_SLICE_A_COLS") == "0":
+        fewer than all of them (syc 32 5 at 8 ranks: 2^13 of 2^16); else None. QKNIT_SLICE_A_COLS=0
+        compresses and checks all columns (A/B)."""
+        if self.mode != "slice" or self.sharded or os.environ.get("QKNIT_SLICE_A_COLS") == "0":
             return None
         base, n = self._slice_exact_plan()[0][:2]
         width = 1 << len(self.ops.clbits[self.order[0]])
@@ -1532,7 +1544,7 @@ class KnitPipeline:
         """Per side of the exact slice contraction: (the output bits' column range [base, base + n) of
         that side this rank's slice reads, whether it is the rank's own column block, device keys of
         those columns relative to the slice start). Built once."""
-        if getattr(self, "_exact_plan", None) is None:
+        if self._exact_plan is None:
             from .knit_plan import deposit_keys
 
             o_begin, o_count = self.slice
@@ -1585,7 +1597,7 @@ class KnitPipeline:
             return tuple(parts)
         on_gpu = XA.device.type == "cuda"
         if on_gpu:
-            if getattr(self, "_exact_stream", None) is None:
+            if self._exact_stream is None:
                 self._exact_stream = T.cuda.Stream(device=XA.device)
             H = self._exact_stream
             H.wait_stream(T.cuda.current_stream())
@@ -1611,9 +1623,9 @@ class KnitPipeline:
 
         return finish
 
-    def _exact_mats(self, p: dict):
+    def _exact_mats(self, p: PreparedStep):
         """(X_A, X_B): the transformed operands of a prepared step, row side first."""
-        return p["mats"][self.order[0]], p["mats"][self.order[-1]]
+        return p.mats[self.order[0]], p.mats[self.order[-1]]
 
     def _slice_exact(self, XA, XB, cA, cB):
         """Exact contraction of this rank's output slice (K terms) from the transformed column blocks
@@ -1633,15 +1645,7 @@ class KnitPipeline:
         waits for the device; round 4 read every 32 steps back, which drained the pipelined multi-GPU
         queue each time). In slice mode k_eff is MIN-all-reduced in place afterwards, so the tally is
         queued there after that reduction (_prep_slice)."""
-        T = self.T
-        self._tally_for(k_eff.device)
-        tally = getattr(self.be, "rank_tally", None)
-        if tally is not None:
-            tally(r, k_eff, self._tally)
-        else:  # host backends (CPU tests): the same counts with torch
-            rv, kv = int(r.reshape(-1)[0]), int(k_eff.reshape(-1)[0])
-            self._tally += T.tensor([int(rv == 0), int(rv > 0 and kv == 0), 0, 1], dtype=T.int64)
-            self._tally[2] = kv
+        self.be.rank_tally(r, k_eff, self._tally_for(k_eff.device))
         self._pending += 1
 
     def sync_stats(self):
@@ -1724,10 +1728,10 @@ class KnitPipeline:
                                       strideB=1, out=self.out)
         cA, cB = self.ops.clbits[ia], self.ops.clbits[ib]
         stream = os.environ.get("QKNIT_OUTER", "stream") == "stream"  # "paired": keyed kernel (A/B timing)
-        if stream and r <= 8 and engine.stream_knit_ok(cA, cB, self.N) and hasattr(self.be, "knit_outer_stream"):
-            self.last_kernel = self._kernel_name(r, cA, cB)
+        if stream and r <= 8 and engine.stream_knit_ok(cA, cB, self.N) and "knit_outer_stream" in self.be.routes:
+            self.last_kernel = self.be.outer_stream_kernel(r, cA, cB, self.N)
             return self.be.knit_outer_stream(A, B, cA, cB, self.N, self.out)
-        if r <= 8 and engine.paired_keys(cB) and hasattr(self.be, "gemm_outer_paired"):
+        if r <= 8 and engine.paired_keys(cB) and "gemm_outer_paired" in self.be.routes:
             st = engine._affine_stride(cA)
             kA = None if st is not None else engine._device_keys(tuple(cA), None, None, A.device)
             kB = engine._device_keys(tuple(cB), None, None, B.device)
@@ -1764,13 +1768,12 @@ class KnitPipeline:
         """A fresh [n] fp64 device buffer for the knit output (engine.out_buffer: 1-GiB-mapped when
         large; a host backend's own allocation in the CPU tests). ``self.out_alloc`` records how.
         ``select=False``: a large mapping is not write-rate checked (take_out's first call)."""
-        alloc = getattr(self.be, "out_buffer", None)
-        if alloc is None:
+        if "out_buffer" not in self.be.routes:  # a host backend's own allocation
             self.out_alloc = "backend"
             self._last_owner = None
             return self.be.zeros((n,), self.T.float64) if zero else self.be.empty((n,), self.T.float64)
         n_sel = len(engine.out_selections)
-        out, owner = alloc(n) if select else alloc(n, select=False)
+        out, owner = self.be.out_buffer(n, select=select)
         self.out_alloc = "qk_out_alloc (1-GiB mapped chunks)" if owner is not None else "torch"
         if len(engine.out_selections) > n_sel:  # candidates' write rates, the kept one first
             last = engine.out_selections[-1]
@@ -1793,7 +1796,7 @@ class KnitPipeline:
         reports it (:meth:`note_call_write`), and a slow buffer is replaced at a later call."""
         n = self.slice[1] if self.mode == "slice" else 1 << self.N
         zero = not self.covers_outputs()
-        own = getattr(self, "_call_owner", None)
+        own = self._call_owner
         if own is not None and own.n == n and not own.in_use():
             if getattr(own, "write_gbs", None) is None or own.write_gbs >= engine.OUT_FAST_GBS:
                 out = own.tensor()
@@ -1819,10 +1822,10 @@ class KnitPipeline:
     def note_call_write(self, events_before: int):
         """After a drop-in call whose output mapping was not write-rate checked (take_out): the rate of
         the call's own write (its HIP events) decides whether later calls keep the mapping."""
-        if not getattr(self, "_time_call_write", False):
+        if not self._time_call_write:
             return
         self._time_call_write = False
-        own = getattr(self, "_call_owner", None)
+        own = self._call_owner
         ev = self.events[events_before:]
         if own is None or not ev:
             return
@@ -1893,7 +1896,7 @@ class KnitPipeline:
         """(row side, column side) fragment indices when the dict result can be selected straight
         from the two knit operands (qk_knit_select): two live fragments, ascending disjoint clbits."""
         live = [i for i, fs in enumerate(self.frags) if not fs.dropped]
-        if self.mode != "single" or len(live) != 2 or len(self.order) != 2 or not hasattr(self.be, "knit_select"):
+        if self.mode != "single" or len(live) != 2 or len(self.order) != 2 or "knit_select" not in self.be.routes:
             return None
         ia, ib = self.order[0], self.order[-1]
         cA, cB = list(self.ops.clbits[ia]), list(self.ops.clbits[ib])
@@ -1918,12 +1921,12 @@ class KnitPipeline:
         if pair is not None and self.dev_rank:
             p = self._prep_dev_rank(qs)
             ia, ib = pair
-            keys, vals = self.be.knit_select(p["A2"], p["B2"], self.ops.clbits[ia], self.ops.clbits[ib], self.N,
-                                             accuracy, k_dev=p["k_eff"])
+            keys, vals = self.be.knit_select(p.A2, p.B2, self.ops.clbits[ia], self.ops.clbits[ib], self.N,
+                                             accuracy, k_dev=p.k_eff)
             self.last_kernel = "qk_knit_select_kernel"
-            if int(p["k_eff"].reshape(-1)[0]) > 0:
+            if int(p.k_eff.reshape(-1)[0]) > 0:
                 return self.be.npd_pairs(keys, vals)
-            mats = p["mats"]  # rejected compression: the exact contraction, dense
+            mats = p.mats  # rejected compression: the exact contraction, dense
         else:
             mats = self.operands(qs)
             if pair is not None and mats[pair[0]].shape[0] <= 8:
@@ -1940,7 +1943,6 @@ class KnitPipeline:
             return self.be.npd_dense(dense, accuracy)
         finally:
             self.out = keep
-
 
     def _knit_dict_slice(self, accuracy: float, qs):
         """knit_dict in slice mode (multi-GPU; every rank returns the whole result, ``run.py:71``): each
@@ -1963,12 +1965,12 @@ class KnitPipeline:
         o_begin, o_count = self.slice
         p = self._prep_step(qs) if self.dev_rank else None
         keys = vals = None
-        if p is not None and int(p["k_eff"].reshape(-1)[0]) > 0:
+        if p is not None and int(p.k_eff.reshape(-1)[0]) > 0:
             (bA, nA, _, _), (bB, nB, _, _) = self._slice_exact_plan()
             cA, cB = list(self.ops.clbits[ia]), list(self.ops.clbits[ib])
             # the column ranges are the low log2(n) bits of each side's index (aligned blocks)
-            keys, vals = be.knit_select(p["A2"][:, bA:bA + nA], p["B2"][:, bB:bB + nB], cA[:nA.bit_length() - 1],
-                                        cB[:nB.bit_length() - 1], self.N, accuracy, k_dev=p["k_eff"])
+            keys, vals = be.knit_select(p.A2[:, bA:bA + nA], p.B2[:, bB:bB + nB], cA[:nA.bit_length() - 1],
+                                        cB[:nB.bit_length() - 1], self.N, accuracy, k_dev=p.k_eff)
             keys = keys + o_begin
             self.last_kernel = "qk_knit_select_kernel"
         else:
@@ -2009,9 +2011,7 @@ class KnitPipeline:
         return be.npd_pairs(ku, vu)
 
     def step(self):
-        bind = getattr(self.be, "bind", None)
-        if bind is not None:  # the caller may have switched torch's current stream since the last step
-            bind()
+        self.be.bind()  # the caller may have switched torch's current stream since the last step
         if self.overlap and self.overlap_ok():
             return self._step_overlapped()
         if not self.record_events:
@@ -2064,8 +2064,7 @@ class KnitPipeline:
         from . import sweep_plan
 
         hbm = alg = flops = 0
-        shared = dict(zip(getattr(self, "_multi", None)[0], getattr(self.be, "shared_init", None) or [])) \
-            if getattr(self, "_multi", None) is not None else {}
+        shared = dict(zip(self._multi[0], self.be.shared_init or [])) if self._multi is not None else {}
         for i, (fs, sw) in enumerate(zip(self.frags, self.sweeps)):
             if sw is None or not sw["n_jobs"]:
                 continue

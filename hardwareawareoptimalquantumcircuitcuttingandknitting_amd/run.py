@@ -209,10 +209,10 @@ def _plan_held_bytes(pipe) -> int:
     """Device bytes a cached plan holds: its buffers, the output mapping it keeps for reuse (the mapped
     bytes: whole 1-GiB chunks) and the output buffers of pipelined steps, if any."""
     total = pipe.plan_bytes()
-    own = getattr(pipe, "_call_owner", None)
+    own = pipe._call_owner
     if own is not None:
         total += own.mapped_bytes() if hasattr(own, "mapped_bytes") else 8 * own.n
-    for t in getattr(pipe, "_outs", None) or []:
+    for t in pipe._outs or []:
         total += t.numel() * t.element_size()
     return total
 
@@ -245,7 +245,7 @@ def _planned_dense(virt: VirtualCircuit, device: int, out):
     t_out = perf_counter()
     e0, e1 = T.cuda.Event(enable_timing=True), T.cuda.Event(enable_timing=True)
     host = perf_counter() - now
-    timed = getattr(pipe, "_time_call_write", False) and not pipe.record_events
+    timed = pipe._time_call_write and not pipe.record_events
     n_ev = len(pipe.events)
     e0.record()
     pipe.out = out
@@ -353,9 +353,7 @@ def run_virtual_circuit_sharded(virt: VirtualCircuit, group=None, *, device: int
     on_gpu = backend is None
     now = perf_counter()
     pipe = cached_plan(virt, device, group="WORLD" if group is None else group, backend=backend)
-    bind = getattr(pipe.be, "bind", None)
-    if bind is not None:
-        bind()
+    pipe.be.bind()
     # slice mode: the previous call's output mapping again once the caller dropped it (take_out);
     # reduce mode: a fresh (small) buffer per call, as the reference returns a new result per call
     pipe.out = pipe.take_out() if pipe.mode == "slice" else None

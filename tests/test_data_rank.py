@@ -174,3 +174,43 @@ def test_data_rank_off_outside_single_mode():
     assert not KnitPipeline(VirtualCircuit(cut), factored=True, backend=CpuBackend(), data_rank=False).data_rank
     # default: small outputs (< 2^24) keep the exact contraction
     assert not KnitPipeline(VirtualCircuit(cut), factored=True, backend=CpuBackend()).data_rank
+
+
+def test_backend_contract_rejects_misspelt_and_missing_operations():
+    """A Backend subclass is checked where it is defined: an operation the contract does not know (a
+    misspelt one), a declared route without its methods, an unknown route and a missing required
+    operation are TypeErrors; the product backend and the CPU model pass and declare their routes."""
+    from cpu_backend import CpuBackend
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.pipeline import Backend, HipBackend
+
+    assert HipBackend.routes == frozenset(Backend.ROUTES) and HipBackend.fuses_tally
+    assert "plan_multi" not in CpuBackend.routes and not CpuBackend.fuses_tally
+    assert CpuBackend().compress_v(None, None, None, None, None) is None
+    with pytest.raises(TypeError, match="compres_v is not a Backend operation"):
+        type("Misspelt", (CpuBackend,), {"compres_v": lambda self, *a, **k: None})
+    with pytest.raises(TypeError, match="missing knit_select; missing npd_pairs"):
+        type("NoMethod", (CpuBackend,), {"routes": CpuBackend.routes | {"knit_select"}})
+    with pytest.raises(KeyError, match="rank_factor"):
+        type("BadRoute", (CpuBackend,), {"routes": frozenset({"rank_factor"})})
+    with pytest.raises(TypeError, match="missing sweep"):
+        type("Empty", (Backend,), {})
+
+
+def test_backend_adopts_a_duck_typed_object():
+    """A backend object whose class does not derive from Backend still drives the pipeline: it gets the
+    contract's defaults and the routes whose operations it defines, and the same distribution comes out."""
+    from cpu_backend import CpuBackend
+    from oracle import dense
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.pipeline import Backend, KnitPipeline
+
+    skip = {"sweep_rows", "prep_operands"}
+    Duck = type("Duck", (), {n: v for n, v in vars(CpuBackend).items() if n not in skip | {"routes"}})
+    _, cut = _case("hwe_p2")
+    pipe = KnitPipeline(VirtualCircuit(cut), factored=True, backend=Duck(), data_rank=True)
+    assert isinstance(pipe.be, Backend) and isinstance(pipe.be, Duck)
+    assert pipe.be.routes == CpuBackend.routes - skip and pipe.dev_rank
+    np.testing.assert_allclose(pipe.step().numpy(), dense.run_dense(cut), atol=1e-12, rtol=0)
+    assert pipe.last_prep == "torch" and pipe.last_kernel == "Duck"

@@ -659,17 +659,17 @@ def test_gemm_outer_paired_matches_torch(T, K, odd_rows):
 
 @pytest.mark.parametrize("case", ["cx_6x6_3cuts", "cx_8x8_2cuts", "syc_16"])
 @pytest.mark.parametrize("reject", [False, True])
-def test_speculative_write_matches_oracle(T, case, reject):
-    """Speculative write (QKNIT_SPEC_WRITE): the write runs at the factored rank while the probe check
-    runs on a side stream; a rejected check (rank_tol NaN) or an incompressible knit (syc_16: rank
-    above 8) still ends in the exact contraction over every output. Equal to the oracle (1e-12)."""
+def test_device_rank_step_matches_oracle(T, case, reject):
+    """The default device-rank step (probe check, then the write at the accepted rank, then the
+    predicated exact contraction) with the torch preparation (cx_6x6_3cuts) and the fused one: a
+    rejected check (rank_tol NaN) or an incompressible knit (syc_16: rank above 8) still ends in the
+    exact contraction over every output. Equal to the oracle (1e-12)."""
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.pipeline import KnitPipeline
 
     cut = {"cx_6x6_3cuts": lambda: circuits.two_fragment("cx", 6, 6, n_cuts=3)[1],
            "cx_8x8_2cuts": lambda: circuits.two_fragment("cx", 8, 8, n_cuts=2)[1],
            "syc_16": lambda: circuits.two_fragment("cx", 8, 8, n_cuts=4)[1]}[case]()
     pipe = KnitPipeline(VirtualCircuit(cut), factored=True, data_rank=True)
-    pipe.spec_write = True
     if reject:
         pipe.rank_tol = pipe.rank_tol_rel = float("nan")
     ref = dense.run_dense(cut)
@@ -681,7 +681,6 @@ def test_speculative_write_matches_oracle(T, case, reject):
     pipe.sync_stats()
     assert pipe.dev_rank
     if pipe.last_prep == "fused":
-        assert pipe._spec_stream is not None  # the check ran beside the write
         if reject:
             assert pipe.rank_fallbacks + pipe.rank_incompressible == 3 and pipe.last_rank is None
         elif case == "syc_16":
@@ -1240,43 +1239,6 @@ def test_prep_operands_matches_torch(T, K, RA, RB, NA, NB):
             engine.prep_operands(ctx, WtA[:, :5].contiguous(), qA, WtB[:, :5].contiguous(), qB, P)
 
 
-@pytest.mark.parametrize("K,RA,RB,NA,NB,rmax", [(64, 65, 65, 65536, 65536, 8), (64, 80, 17, 1024, 2048, 8),
-                                                (6, 1, 9, 512, 512, 3), (64, 64, 64, 8192, 1536, 1), (32, 33, 48, 512, 4096, 8)])
-def test_qprep_matches_torch(T, K, RA, RB, NA, NB, rmax):
-    """The q-space preparation (qk_qprep_grams, qk_qprep_compress_check: no X = Wt^T q materialised) against
-    torch fp64 on the X path's definitions: the Grams of X, U = X_B P^T, A2 = TA X_A, B2 = TB X_B and the
-    probe check's squared errors (via the accepted rank at a tolerance set around them); deterministic.
-    Shapes: syc 32 5's two sides (65 swept rows each), the 80-row maximum, one row, K < 16, rmax < 8."""
-    ctx = engine.get_context(0)
-    g = T.Generator(device="cuda").manual_seed(K + RA + RB + NA)
-    WtA = T.randn(RA, K, dtype=T.float64, device="cuda", generator=g)
-    WtB = T.randn(RB, K, dtype=T.float64, device="cuda", generator=g)
-    qA = T.randn(RA, NA, dtype=T.float64, device="cuda", generator=g)
-    qB = T.randn(RB, NB, dtype=T.float64, device="cuda", generator=g)
-    P = T.randn(16, NB, dtype=T.float64, device="cuda", generator=g)
-    G, U = engine.qprep_grams(ctx, WtA, qA, WtB, qB, P)
-    T.cuda.synchronize()
-    XA, XB = WtA.T @ qA, WtB.T @ qB
-    close = lambda a, b: float((a - b).abs().max()) <= 1e-13 * max(float(b.abs().max()), 1.0) * 64  # noqa: E731
-    assert close(G[0], XA @ XA.T) and close(G[1], XB @ XB.T)
-    assert close(U, XB @ P.T)
-    TA = T.randn(rmax, K, dtype=T.float64, device="cuda", generator=g)
-    TB = T.randn(rmax, K, dtype=T.float64, device="cuda", generator=g)
-    r = T.tensor([rmax], dtype=T.int32, device="cuda")
-    A2, B2, k, err = engine.qprep_compress_check(ctx, WtA, qA, WtB, qB, TA, TB, U, P, r, 1e300, 0.0)
-    T.cuda.synchronize()
-    assert close(A2, TA @ XA) and close(B2, TB @ XB)
-    d = XA.T @ (XB @ P.T) - A2.T @ (B2 @ P.T)
-    ref_err = float((d * d).sum(dim=0).max().sqrt())
-    assert int(k) == rmax and abs(float(err) - ref_err) <= 1e-9 * ref_err
-    _, _, k2, _ = engine.qprep_compress_check(ctx, WtA, qA, WtB, qB, TA, TB, U, P, r, 0.5 * ref_err, 0.0)
-    assert int(k2) == 0  # the same error against half of it: rejected
-    G2, U2 = engine.qprep_grams(ctx, WtA, qA, WtB, qB, P)
-    A22, B22, _, err2 = engine.qprep_compress_check(ctx, WtA, qA, WtB, qB, TA, TB, U, P, r, 1e300, 0.0)
-    T.cuda.synchronize()
-    assert T.equal(G, G2) and T.equal(U, U2) and T.equal(A2, A22) and T.equal(B2, B22) and T.equal(err, err2)
-
-
 @pytest.mark.parametrize("K,NA,NB,rmax", [(64, 4096, 1001, 8), (24, 129, 8192, 8), (64, 65536, 65536, 8),
                                           (24, 4096, 2048, 3), (17, 2050, 130, 8), (64, 2048, 4096, 1)])
 def test_compress_operands_matches_torch(T, K, NA, NB, rmax):
@@ -1675,19 +1637,15 @@ def test_knit_lowrank_c_entry_matches_oracle(T, case, reject):
 
 
 @pytest.mark.slow
-@pytest.mark.parametrize("qprep", [False, True])
-def test_knit_lowrank_c_entry_syc_32_5_equals_bench_step(T, qprep, monkeypatch):
+def test_knit_lowrank_c_entry_syc_32_5_equals_bench_step(T):
     """The one-call C entry on the headline workload writes the bench step's distribution bit for bit
-    (same kernels, same probes and tolerances, chained in C instead of Python) — with the default
-    X-path preparation and with the opt-in q-space chain (QKNIT_QPREP=1) on both sides."""
+    (same kernels, same probes and tolerances, chained in C instead of Python)."""
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.pipeline import KnitPipeline
 
-    monkeypatch.setattr(engine, "QPREP", qprep)
-    monkeypatch.setenv("QKNIT_QPREP", "1" if qprep else "0")
     cut = cutting.config_cut_circuit("syc", 32, 5, 2, "ref")[1]
     pipe = KnitPipeline(VirtualCircuit(cut), factored=True)
     ref = pipe.step()
-    assert pipe.last_prep == ("qspace" if qprep else "fused")
+    assert pipe.last_prep == "fused"
     out, rank = engine.knit_lowrank_c(engine.get_context(0), pipe, pipe.sweep())
     assert 1 <= int(rank.item()) <= 8
     assert _chunked_max_abs_diff(out, ref) == 0.0

@@ -2,7 +2,7 @@
 """A/B of pipeline step settings in one process, into one output buffer (small deltas need that:
 the write's rate depends on the buffer).
 
-    python tools/ab_step.py [--workload syc_32_5_p2] [--steps 20] [--rounds 3] --settings spec_write=0 spec_write=1
+    python tools/ab_step.py [--workload syc_32_5_p2] [--steps 20] [--rounds 3] --settings "" ENV:QKNIT_COMPRESS_V=0
 
 A setting is ``attr=value`` on the KnitPipeline (ints / floats parsed) or ``ENV:VAR=value``; settings are
 timed in turn, ``--rounds`` times, each as ``--steps`` plain steps between device syncs. Prints one JSON
@@ -54,7 +54,7 @@ def main():
     ap.add_argument("--workload", default="syc_32_5_p2")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--settings", nargs="+", default=["", "spec_write=1"])
+    ap.add_argument("--settings", nargs="+", default=["", "ENV:QKNIT_COMPRESS_V=0"])
     ap.add_argument("--builds", nargs="*", default=[],
                     help="one pipeline per build setting 'NAME=v' (a pipeline-module constant set before the "
                          "pipeline is built, e.g. ROW_JOBS=0); all of them write into the first one's output "

@@ -32,7 +32,7 @@ def main():
     qs = pipe.sweep()
     p_ = pipe._prep_dev_rank(qs)
     torch.cuda.synchronize()
-    A2, B2, k = p_["A2"], p_["B2"], p_["k_eff"]
+    A2, B2, k = p_.A2, p_.B2, p_.k_eff
     cA, cB = pipe.ops.clbits[pipe.order[0]], pipe.ops.clbits[pipe.order[-1]]
     N = pipe.N
     del pipe

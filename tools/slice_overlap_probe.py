@@ -36,7 +36,7 @@ def main():
     qs = pipe.sweep()
     p_ = pipe._prep_dev_rank(qs)
     torch.cuda.synchronize()
-    A2, B2, k = p_["A2"], p_["B2"], p_["k_eff"]
+    A2, B2, k = p_.A2, p_.B2, p_.k_eff
     ia, ib = pipe.order[0], pipe.order[-1]
     cA, cB = pipe.ops.clbits[ia], pipe.ops.clbits[ib]
     N = pipe.N
