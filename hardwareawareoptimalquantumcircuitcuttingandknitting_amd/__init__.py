@@ -28,12 +28,12 @@ from .virtual_gates import (
 )
 from .virtual_circuit import VirtualCircuit, generate_instantiations
 from .run import (RunTimeInfo, run_virtual_circuit, run_virtual_circuit_dense, run_virtual_circuit_expectation,
-                  run_virtual_circuit_marginal)
+                  run_virtual_circuit_marginal, run_virtual_circuit_shots)
 
 __all__ = [
     "ClassicalRegister", "QuantumCircuit", "QuantumRegister", "QuasiDistr", "RZZ_ACCURACY",
     "VIRTUAL_GATE_TYPES", "VirtualBinaryGate", "VirtualCPhase", "VirtualCX", "VirtualCY",
     "VirtualCZ", "VirtualGateEndpoint", "VirtualMove", "VirtualRZZ", "WireCut", "VirtualCircuit",
     "generate_instantiations", "RunTimeInfo", "run_virtual_circuit", "run_virtual_circuit_dense",
-    "run_virtual_circuit_marginal", "run_virtual_circuit_expectation",
+    "run_virtual_circuit_marginal", "run_virtual_circuit_expectation", "run_virtual_circuit_shots",
 ]

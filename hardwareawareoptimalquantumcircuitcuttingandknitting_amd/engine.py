@@ -750,6 +750,80 @@ def sample_fragment(ctx: Context, fs: "FragmentState", shots: int, seed: int, ac
     return q
 
 
+def uniforms(ctx: Context, seed: int, label: int, first: int, n: int):
+    """``qk_uniforms``: device float64 ``[n]`` of ``u(seed, label, first + i)``, the counter-based stream
+    of :func:`sample_fragment` (``oracle.sampling.uniforms`` on the host)."""
+    T = torch()
+    label, first, n = int(label), int(first), int(n)
+    if label < 0 or first < 0 or n < 0:
+        raise ValueError(f"label, first and n must not be negative ({label}, {first}, {n})")
+    u = T.empty(n, dtype=T.float64, device=T.device("cuda", ctx.device))
+    ctx.check(ctx.lib.qk_uniforms(ctx.handle, int(seed) & _U64, label, first, n, u.data_ptr()), "qk_uniforms")
+    return u
+
+
+SAMPLE_ROWS_WORK_BYTES = 256 << 20  # workspace of one qk_sample_rows launch: rows beyond it go in chunks
+
+
+def sample_rows(ctx: Context, X, C, draw_off, u, m: int | None = None):
+    """``qk_sample_rows``: inverse-CDF draws from the rows of ``max(C @ X, 0)`` without storing it.
+    ``X``: float64 ``[K, 2^m]``, ``C``: float64 ``[n_rows, K]``, both with unit column stride (their row
+    strides are ``ldx`` / ``ldc``; with ``m`` given, ``X`` may be wider than ``2^m``); ``draw_off``: int64
+    ``[n_rows + 1]``, ascending from 0 to ``len(u)``: row r owns the draws ``draw_off[r]:draw_off[r + 1]``;
+    ``u``: float64 ``[n_draws]`` in [0, 1). All on the device and only read. Returns ``(x, w, row_total)``:
+    int64 ``[n_draws]`` the first x whose inclusive prefix sum exceeds ``u * row_total`` (-1 for a row
+    whose total is not > 0), float64 ``[n_draws]`` its weight, float64 ``[n_rows]`` the row sums."""
+    T = torch()
+    if X.dim() != 2 or X.dtype != T.float64 or X.shape[0] < 1 or (X.shape[1] > 1 and X.stride(1) != 1):
+        raise ValueError("X must be float64 [K >= 1, 2^m] with unit column stride")
+    K = X.shape[0]
+    if m is None:
+        m = X.shape[1].bit_length() - 1
+        if X.shape[1] != 1 << m:
+            raise ValueError(f"X has {X.shape[1]} columns: not a power of two (pass m)")
+    m = int(m)
+    if not 0 <= m <= 30:
+        raise ValueError(f"m must be in 0..30, not {m}")
+    if X.shape[1] < 1 << m:
+        raise ValueError(f"X has {X.shape[1]} columns for m = {m}")
+    if C.dim() != 2 or C.dtype != T.float64 or C.shape[1] != K or (K > 1 and C.stride(1) != 1):
+        raise ValueError("C must be float64 [n_rows, K] with unit column stride")
+    n_rows, n_draws = C.shape[0], u.numel()
+    if draw_off.dtype != T.int64 or draw_off.dim() != 1 or draw_off.numel() != n_rows + 1 or not draw_off.is_contiguous():
+        raise ValueError("draw_off must be contiguous int64 [n_rows + 1]")
+    if u.dtype != T.float64 or u.dim() != 1 or not u.is_contiguous():
+        raise ValueError("u must be contiguous float64 [n_draws]")
+    if any(t.device != X.device for t in (C, draw_off, u)) or not X.is_cuda:
+        raise ValueError("X, C, draw_off and u must be on one HIP device")
+    ldx = X.stride(0) if K > 1 else max(X.stride(0), 1 << m)
+    ldc = C.stride(0) if n_rows > 1 else max(C.stride(0), K)
+    x = T.empty(n_draws, dtype=T.int64, device=X.device)
+    w = T.empty(n_draws, dtype=T.float64, device=X.device)
+    row_total = T.empty(n_rows, dtype=T.float64, device=X.device)
+    if n_rows == 0:
+        if n_draws:
+            raise ValueError("draws without rows")
+        return x, w, row_total
+    per_row = 8 << max(m - 10, 0)  # workspace bytes of a row
+    step = max(1, SAMPLE_ROWS_WORK_BYTES // per_row)
+    off_h = draw_off.cpu().tolist() if step < n_rows else None  # chunks need their draw ranges on the host
+    for r0 in range(0, n_rows, step):
+        r1 = min(r0 + step, n_rows)
+        if off_h is None:
+            d0, d1, off = 0, n_draws, draw_off
+        else:
+            d0, d1 = off_h[r0], off_h[r1]
+            off = draw_off[r0:r1 + 1] - d0
+        need = ctypes.c_int64()
+        ctx.check(ctx.lib.qk_sample_rows_workspace_bytes(r1 - r0, m, ctypes.byref(need)), "qk_sample_rows_workspace_bytes")
+        work = T.empty(need.value // 8, dtype=T.float64, device=X.device)
+        ctx.check(ctx.lib.qk_sample_rows(ctx.handle, K, m, X.data_ptr(), ldx, r1 - r0, C[r0:r1].data_ptr(), ldc,
+                                         off.data_ptr(), d1 - d0, u[d0:d1].data_ptr(), x[d0:d1].data_ptr(),
+                                         w[d0:d1].data_ptr(), row_total[r0:r1].data_ptr(), work.data_ptr(), need.value),
+                  "qk_sample_rows")
+    return x, w, row_total
+
+
 def label_rows(fs: "FragmentState") -> "FragmentState":
     """``fs`` with one row per reference label: the layout of sampled and foreign-backend q_f."""
     return dataclasses.replace(fs, uidx=None, unique_labels=None)

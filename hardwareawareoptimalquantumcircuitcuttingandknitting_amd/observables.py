@@ -165,6 +165,21 @@ def split_mask(mask: int, fragment_clbits: list) -> list:
     return [sum(1 << i for i, c in enumerate(fcl) if mask >> c & 1) for fcl in fragment_clbits]
 
 
+def key_positions(clbits: list, fragment_clbits: list) -> tuple:
+    """For keys whose bit ``i`` is ``clbits[i]``: per fragment ``(keep, where)``, its local ``keep_mask``
+    (as :func:`split_clbits`) and, for its kept local bits in ascending order, their bit of the key."""
+    keep, positions = split_clbits(clbits, fragment_clbits)
+    order = sorted(clbits)
+    return keep, [[clbits.index(order[p]) for p in pos] for pos in positions]
+
+
+def deposit_bits(keys, x, where: list):
+    """``keys`` with bit ``i`` of ``x`` set at bit ``where[i]`` (integer arrays or tensors alike)."""
+    for i, b in enumerate(where):
+        keys = keys | (((x >> i) & 1) << b)
+    return keys
+
+
 def _user_order(T, asc_result, clbits: list):
     """Result indexed with bit i = clbits[i], from the one indexed by the ascending clbits."""
     order = sorted(clbits)
@@ -248,6 +263,50 @@ class KnitReducer:
         for a in mats[1:]:
             prod = prod * a
         return prod.sum(0).cpu().numpy()
+
+    def sample(self, shots: int, seed: int = 0, clbits=None):
+        """``shots`` measurement outcomes of the exact knit: device int64 ``[shots]`` of keys in draw
+        order, bit ``i`` of a key = ``clbits[i]`` (``None``: all clbits, bit i = clbit i). Drawn fragment
+        by fragment (``qk_sample_rows``, DESIGN.md §4a "Shots"): step f draws fragment f's outcome from
+        ``max(sum_k c[k] t_f[k] X_f[k][x], 0)`` with ``u(seed, f, shot)``, ``c`` the product of the earlier
+        fragments' columns at their drawn outcomes and ``t_f`` the later fragments' row sums. A pure
+        function of (circuit, seed, shot index): nothing of size 2^N is formed. ``RuntimeError`` if a
+        conditional distribution has no positive weight."""
+        self.ctx.bind_stream()
+        T = engine.torch()
+        dev = T.device("cuda", self.device)
+        shots = int(shots)
+        if shots < 0:
+            raise ValueError(f"shots must not be negative, not {shots}")
+        cl = list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+        keys = T.zeros(shots, dtype=T.int64, device=dev)
+        if shots == 0 or not self.frags:
+            return keys
+        keep, where = key_positions(cl, self.clbits)
+        mats = self._operands(keep, [[0]] * len(keep))  # X_f [K, 2^k_f]
+        sums = [engine.reduce_bits(self.ctx, X, len(pos), 0, [0])[:, 0] for X, pos in zip(mats, where)]
+        tails = [None] * len(mats)  # t_f[k] = prod_{g > f} s_g[k]
+        tail = T.ones(mats[0].shape[0], dtype=T.float64, device=dev)
+        for f in reversed(range(len(mats))):
+            tails[f] = tail
+            tail = tail * sums[f]
+        c = T.ones((shots, mats[0].shape[0]), dtype=T.float64, device=dev)
+        for f, (X, pos) in enumerate(zip(mats, where)):
+            # shots with the same prefix share a row; a row's draws are in shot order
+            _, inv, counts = T.unique(keys, return_inverse=True, return_counts=True)
+            by_row = T.argsort(inv, stable=True)
+            draw_off = T.zeros(counts.numel() + 1, dtype=T.int64, device=dev)
+            T.cumsum(counts, 0, out=draw_off[1:])
+            C = c[by_row[draw_off[:-1]]] * tails[f]
+            u = engine.uniforms(self.ctx, seed, f, 0, shots)[by_row]
+            xs, _, _ = engine.sample_rows(self.ctx, X, C, draw_off, u, m=len(pos))
+            if bool((xs < 0).any()):
+                raise RuntimeError(f"fragment {f}: a conditional distribution of the knit has no positive weight")
+            x = T.empty_like(xs)
+            x[by_row] = xs
+            c = c * X[:, x].T
+            keys = deposit_bits(keys, x, pos)
+        return keys
 
     def marginal_parity(self, clbits, masks):
         """The mixed form: device fp64 ``[M, 2^k]``, row j the marginal onto ``clbits`` of

@@ -550,3 +550,28 @@ def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device
     info = RunTimeInfo(run_time, perf_counter() - now)
     log.info("Knitted in %.2fs.", info.knit_time)
     return vals, info
+
+
+def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed: int = 0, clbits=None,
+                              memory: bool = False, device: int = 0, factored: bool | None = None, group=None,
+                              sample: bool = False):
+    """``shots`` measurement outcomes distributed as the exact knit, i.e. as the uncut circuit's output,
+    without the 2^N distribution: drawn fragment by fragment from the swept rows
+    (:meth:`observables.KnitReducer.sample`, ``qk_sample_rows``). Not ``run_virtual_circuit(sample=True)``,
+    which samples the fragment instances and knits the noisy rows. Returns ``(result, RunTimeInfo)``; the
+    sweep is ``run_time``, the chain of draws ``knit_time``.
+
+    ``memory=False``: counts ``{key: count}`` (Python ints); ``memory=True``: the device int64 tensor
+    ``[shots]`` of keys in draw order. ``clbits``: the measured clbits (bit ``i`` of a key = ``clbits[i]``),
+    ``None`` = all. A pure function of (circuit, ``seed``, ``shots``); the first ``n`` shots of a longer
+    run are an ``n``-shot run. Same restrictions as :func:`run_virtual_circuit_marginal`."""
+    red, run_time = _reducer(virt, device, factored, group, sample)
+    now = perf_counter()
+    keys = red.sample(shots, seed, clbits)
+    if memory:
+        _sync(device)
+        return keys, RunTimeInfo(run_time, perf_counter() - now)
+    uniq, counts = engine.torch().unique(keys, return_counts=True)
+    info = RunTimeInfo(run_time, perf_counter() - now)
+    log.info("Knitted in %.2fs.", info.knit_time)
+    return dict(zip(uniq.tolist(), counts.tolist())), info

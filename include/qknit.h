@@ -503,6 +503,25 @@ int qk_reduce_bits(qk_ctx* ctx, int64_t rows, int m, const double* src, int64_t 
                    int64_t n_flips, const uint64_t* flip_masks, double* dst, int64_t ld_dst, void* work,
                    int64_t work_bytes);
 
+/* ---- draws from rows of a product that is never stored (qknit_shots.hip): shots from the knit ---
+ * u[i] = u(seed, label, first + i) for i < n: the counter-based stream of qk_sample_counts (DEVICE u). */
+int qk_uniforms(qk_ctx* ctx, uint64_t seed, int64_t label, int64_t first, int64_t n, double* u);
+
+/* w[r][x] = max(sum_{k<K} C[r * ldc + k] * X[k * ldx + x], 0) for r < n_rows, x < 2^m, never stored.
+ * Row r owns the draws [draw_off[r], draw_off[r + 1]) (possibly none); for draw d of row r
+ *   x_out[d] = the first x, ascending, whose inclusive prefix sum of w[r] exceeds u[d] * row_total[r],
+ *   w_out[d] = w[r][x_out[d]],   row_total[r] = sum_x w[r][x];
+ * a row whose total is not > 0 gives x_out = -1, w_out = 0 for its draws. 0 <= m <= 30, K >= 1,
+ * ldx >= 2^m, ldc >= K, 0 <= u < 1, draw_off ascending with draw_off[0] = 0, draw_off[n_rows] = n_draws.
+ * All buffers but ctx are DEVICE pointers; X, C, draw_off and u are only read. `work` holds one double
+ * per row and tile of 2^10 outcomes: n_rows * 2^max(m - 10, 0) doubles (qk_sample_rows_workspace_bytes).
+ * Deterministic: no atomics, every sum in an order fixed by (K, m); a draw's result depends on its
+ * row's coefficients and its u alone, not on the other rows or draws of the launch. */
+int qk_sample_rows_workspace_bytes(int64_t n_rows, int m, int64_t* bytes);
+int qk_sample_rows(qk_ctx* ctx, int64_t K, int m, const double* X, int64_t ldx, int64_t n_rows, const double* C,
+                   int64_t ldc, const int64_t* draw_off, int64_t n_draws, const double* u, int64_t* x_out,
+                   double* w_out, double* row_total, void* work, int64_t work_bytes);
+
 int qk_hellinger(qk_ctx* ctx, int64_t n, const double* p, const double* q, double* acc3);
 
 #ifdef __cplusplus

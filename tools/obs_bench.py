@@ -5,12 +5,25 @@ route (run_virtual_circuit_dense + a torch reduction of the 2^32 output), same p
 HIP events, 3 warm-up rounds, 20 timed repeats each (median and min-max): KnitReducer.marginal onto
 16 clbits (0..7 and 16..23), KnitReducer.expectation of 64 and of 1024 masks, the dense route for each
 of them, and qk_reduce_bits alone on the larger fragment's swept rows with its achieved read rate
-(rows * 2^m * 8 bytes over its time; the rows are cache resident). ``--out FILE`` writes the JSON."""
+(rows * 2^m * 8 bytes over its time; the rows are cache resident). ``--out FILE`` writes the JSON.
+
+``--shots`` runs the shots leg instead (``--out``: e.g. profiles/obs_bench_shots.json): 20000 shots of
+syc 32 5 through KnitReducer.sample (the whole chain, and qk_sample_rows alone on the widest step's
+operands), beside the only other route to the same thing in the same process: the dense step, a
+torch.cumsum over its 2^32 output and torch.searchsorted of the same number of targets. The three
+kernels of qk_sample_rows are timed separately from a kernel trace of a child process
+(``rocprofv3 --kernel-trace -- python tools/obs_bench.py --shots-child``): per sample() call the sum of
+each kernel's dispatches, median over the calls."""
 import argparse
+import glob
 import json
 import os
 import random
+import shutil
+import sqlite3
+import subprocess
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -29,11 +42,126 @@ def timed(torch, fn, reps=20, warm=3):
     return {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1]}
 
 
+SHOTS, SHOTS_SEED, CHILD_WARM, CHILD_REPS = 20000, 1, 3, 20
+SHOT_KERNELS = ("sr_tile_sums", "sr_tile_scan", "sr_locate")
+
+
+def shots_child():
+    """What the kernel trace sees: CHILD_WARM + CHILD_REPS calls of KnitReducer.sample, nothing else timed."""
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+
+    red = KnitReducer(VirtualCircuit(cutting.config_cut_circuit("syc", 32, 5, 2)[1]))
+    for _ in range(CHILD_WARM + CHILD_REPS):
+        red.sample(SHOTS, SHOTS_SEED)
+    torch.cuda.synchronize()
+
+
+def kernel_split():
+    """Per kernel of qk_sample_rows: dispatches per sample() call and the median over the timed calls
+    of their summed durations (ms), from the rocpd database of a traced child process."""
+    tmp = tempfile.mkdtemp(prefix="obs_bench_shots_")
+    try:
+        cmd = ["rocprofv3", "--kernel-trace", "-d", tmp, "--", sys.executable, os.path.abspath(__file__), "--shots-child"]
+        proc = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        dbs = glob.glob(os.path.join(tmp, "**", "*_results.db"), recursive=True)
+        if proc.returncode != 0 or not dbs:
+            raise RuntimeError(f"kernel trace failed (rc {proc.returncode}): {proc.stderr[-500:]}")
+        out = {}
+        for db in dbs:
+            rows = sqlite3.connect(db).execute("select name, duration from kernels order by start").fetchall()
+            for kern in SHOT_KERNELS:
+                durs = [d / 1e6 for name, d in rows if kern in name]
+                if not durs:
+                    continue
+                per_call, rest = divmod(len(durs), CHILD_WARM + CHILD_REPS)
+                if rest:
+                    raise RuntimeError(f"{kern}: {len(durs)} dispatches over {CHILD_WARM + CHILD_REPS} calls")
+                calls = sorted(sum(durs[i * per_call:(i + 1) * per_call]) for i in range(CHILD_WARM, CHILD_WARM + CHILD_REPS))
+                out[kern] = {"dispatches_per_call": per_call, "median_ms": calls[len(calls) // 2], "min_ms": calls[0],
+                             "max_ms": calls[-1]}
+        if set(out) != set(SHOT_KERNELS):
+            raise RuntimeError(f"kernel trace holds {sorted(out)} of {SHOT_KERNELS}")
+        return out
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def shots_leg(args):
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.run import run_virtual_circuit_dense
+
+    res = {"config": "syc_32_5_p2", "device": torch.cuda.get_device_name(0), "reps": 20, "shots": SHOTS}
+    res["qk_sample_rows_kernels"] = kernel_split()  # first: the child needs the memory the dense route takes later
+    _, cut, _ = cutting.config_cut_circuit("syc", 32, 5, 2)
+    virt = VirtualCircuit(cut)
+    red = KnitReducer(virt)
+    ctx = engine.get_context(0)
+    res["fragments"] = [{"rows": int(q.shape[0]), "m": len(cl)} for q, cl in zip(red.qs, red.clbits)]
+    res["terms"] = int(red.ops.num_terms)
+    keys = red.sample(SHOTS, SHOTS_SEED)
+    res["distinct_keys"] = int(torch.unique(keys).numel())
+    res["sample_chain"] = timed(torch, lambda: red.sample(SHOTS, SHOTS_SEED))
+
+    # qk_sample_rows alone on the last step's operands: one row per distinct prefix, K terms, 2^m outcomes
+    mats = red._operands([(1 << len(cl)) - 1 for cl in red.clbits], [[0]] * len(red.clbits))
+    f = len(mats) - 1
+    lead = sum(1 << c for cl in red.clbits[:f] for c in cl)
+    pre, inv, counts = torch.unique(keys & lead, return_inverse=True, return_counts=True)
+    by_row = torch.argsort(inv, stable=True)
+    off = torch.zeros(counts.numel() + 1, dtype=torch.int64, device="cuda")
+    off[1:] = torch.cumsum(counts, 0)
+    C = torch.rand((counts.numel(), mats[f].shape[0]), dtype=torch.float64, device="cuda")
+    u = engine.uniforms(ctx, SHOTS_SEED, f, 0, SHOTS)[by_row]
+    t = timed(torch, lambda: engine.sample_rows(ctx, mats[f], C, off, u))
+    t.update(rows=int(counts.numel()), K=int(mats[f].shape[0]), m=len(red.clbits[f]), draws=SHOTS)
+    t["product_bytes_never_stored"] = t["rows"] * (8 << t["m"])
+    t["fma_per_s"] = t["rows"] * t["K"] * (1 << t["m"]) / t["median_ms"] * 1e3
+    res["qk_sample_rows_last_step"] = t
+
+    if not args.no_dense:
+        u0 = engine.uniforms(ctx, SHOTS_SEED, 0, 0, SHOTS)
+        cdf = torch.empty(1 << 32, dtype=torch.float64, device="cuda")
+
+        def dense_shots():
+            full, _ = run_virtual_circuit_dense(virt)
+            torch.cumsum(full, 0, out=cdf)
+            return torch.searchsorted(cdf, u0 * cdf[-1], right=True)
+
+        def tail_only(full):
+            torch.cumsum(full, 0, out=cdf)
+            return torch.searchsorted(cdf, u0 * cdf[-1], right=True)
+
+        got = dense_shots()
+        res["dense_check"] = {"keys_below_2^32": bool((got < (1 << 32)).all()), "total": float(cdf[-1])}
+        res["dense_step_only"] = timed(torch, lambda: run_virtual_circuit_dense(virt))
+        res["dense_step_cumsum_searchsorted"] = timed(torch, dense_shots)
+        full, _ = run_virtual_circuit_dense(virt)
+        res["cumsum_searchsorted_only"] = timed(torch, lambda: tail_only(full))
+    print(json.dumps(res, indent=1), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-dense", action="store_true", help="skip the dense route (needs 34 GB for the output)")
+    ap.add_argument("--shots", action="store_true", help="the shots leg only (see the module docstring)")
+    ap.add_argument("--shots-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.shots_child:
+        return shots_child()
+    if args.shots:
+        return shots_leg(args)
     import torch
 
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
