@@ -692,6 +692,48 @@ def reduce_bits(ctx: Context, src, m: int, keep_mask: int, flips, out=None):
     return out
 
 
+def wht_rows(ctx: Context, src, m: int | None = None, out=None):
+    """``qk_wht_rows``: ``out[r, z] = sum over x < 2^m of (-1)^popcount(x & z) * src[r, x]``, the
+    unnormalised Walsh-Hadamard transform of every row -> ``[rows, 2^m]``. ``src``: float64
+    ``[rows, >= 2^m]`` with unit column stride; ``m`` defaults to its column count, which must then be a
+    power of two. ``out`` (optional): a float64 tensor with unit column stride and at least ``2^m``
+    columns (further ones stay as they are); ``out is src`` transforms in place; any other overlap with
+    ``src`` is refused."""
+    T = torch()
+    if src.dim() != 2 or src.dtype != T.float64 or (src.shape[1] > 1 and src.stride(1) != 1):
+        raise ValueError("src must be float64 [rows, >= 2^m] with unit column stride")
+    if m is None:
+        cols = src.shape[1]
+        if cols < 1 or cols & (cols - 1):
+            raise ValueError(f"src has {cols} columns, not a power of two: pass m")
+        m = cols.bit_length() - 1
+    m = int(m)
+    if not 0 <= m <= 30:
+        raise ValueError(f"m must be in 0..30, not {m}")
+    n = 1 << m
+    if src.shape[1] < n:
+        raise ValueError("src must be float64 [rows, >= 2^m] with unit column stride")
+    rows = src.shape[0]
+    ld_src = src.stride(0) if rows > 1 else max(src.stride(0), n)
+    if out is None:
+        out = T.empty((rows, n), dtype=T.float64, device=src.device)
+    if out.dim() != 2 or out.dtype != T.float64 or out.shape[0] != rows or out.shape[1] < n or (
+            out.shape[1] > 1 and out.stride(1) != 1) or out.device != src.device:
+        raise ValueError("out must be float64 [rows, >= 2^m] with unit column stride, on the device of src")
+    ld_dst = out.stride(0) if rows > 1 else max(out.stride(0), n)
+    if ld_src < n or ld_dst < n:
+        raise ValueError(f"row stride below 2^m = {n}")
+    if rows == 0:
+        return out
+    if not (src.data_ptr() == out.data_ptr() and ld_src == ld_dst):
+        s0, d0 = src.data_ptr(), out.data_ptr()
+        s1, d1 = s0 + ((rows - 1) * ld_src + n) * 8, d0 + ((rows - 1) * ld_dst + n) * 8
+        if s0 < d1 and d0 < s1:
+            raise ValueError("src and out overlap: only out = src (same rows, same stride) transforms in place")
+    ctx.check(ctx.lib.qk_wht_rows(ctx.handle, rows, m, src.data_ptr(), ld_src, out.data_ptr(), ld_dst), "qk_wht_rows")
+    return out
+
+
 # ----------------------------------------------------------------------------- shot sampling
 _SEED_STRIDE = 0x632BE59BD9B4E019  # per-fragment stream offset (mirrored by oracle/sampling.py)
 _U64 = (1 << 64) - 1

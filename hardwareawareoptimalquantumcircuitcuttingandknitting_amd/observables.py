@@ -13,6 +13,12 @@ csrc/qknit_obs.hip) before the transform ``W_f``; everything after works on narr
 allocates or indexes ``2^N``, so the output width is bounded by the int64 keys (N <= 62), not by
 memory.
 
+Many Z strings at once: a fragment's factor of every string is one entry of its rows' Walsh-Hadamard
+transform, ``H_f[k][z] = sum_x (-1)^popcount(x & z) X_f[k][x]`` (``qk_wht_rows``, csrc/qknit_wht.hip), so
+``<Z_mask> = sum_k prod_f H_f[k][pext(mask, clbits_f)]``: :meth:`KnitReducer.z_spectrum` transforms once,
+then any number of masks is a gather (``expectation(method="spectrum")``, ``expectation_sum``,
+``correlations``).
+
 It builds on the direct path (``engine.prepare_fragments`` / ``sweep_fragment`` / ``knit_operands``
 / ``fragment_operands`` / ``contract``, as ``run._direct_dense``), not on the cached
 ``KnitPipeline``: the pipeline's row pruning rests on a per-entry bound on ``R`` and a marginal sums
@@ -27,6 +33,7 @@ from .backend import MI355XBackend
 from .knit_plan import LabelSpace
 
 MAX_CLBITS = 62  # keys are int64
+SPECTRUM_GATHER_CHUNK = 1 << 20  # masks per gather of the spectrum route: [terms, chunk] doubles per fragment
 
 
 # ----------------------------------------------------------------------------- host index model
@@ -165,6 +172,66 @@ def split_mask(mask: int, fragment_clbits: list) -> list:
     return [sum(1 << i for i, c in enumerate(fcl) if mask >> c & 1) for fcl in fragment_clbits]
 
 
+def masks_array(masks, n_clbits: int) -> np.ndarray:
+    """Z-string observables as an ``int64`` array ``[M]`` of masks over clbits ``0..n_clbits-1``. An
+    integer numpy array or a torch int64 tensor (of any number of masks) is checked vectorised;
+    anything else (ints, ``'IZ'`` strings, lists of them) goes through :func:`parse_masks`."""
+    if type(masks).__module__.split(".")[0] == "torch":
+        masks = masks.detach().cpu().numpy()
+    if isinstance(masks, np.ndarray):
+        if masks.dtype.kind not in "iu":
+            raise ValueError(f"a mask array must hold integers, not {masks.dtype}")
+        if masks.ndim > 1:
+            raise ValueError(f"a mask array must be one-dimensional, not {masks.shape}")
+        zs = np.ascontiguousarray(masks.reshape(-1), dtype=np.int64)  # a uint64 at or above 2^63 turns negative
+        if zs.size and (int(zs.min()) < 0 or int(zs.max()) >> n_clbits):
+            bad = zs[(zs < 0) | ((zs >> min(n_clbits, 63)) != 0)][0]
+            raise ValueError(f"mask {int(bad):#x} outside the {n_clbits} clbits")
+        return zs
+    return np.array(parse_masks(masks, n_clbits), dtype=np.int64).reshape(-1)
+
+
+def split_masks_array(zs: np.ndarray, fragment_clbits: list) -> list:
+    """:func:`split_mask` of every mask of an int64 array at once: per fragment the ``int64`` array
+    ``[M]`` of local masks (a loop over its clbits, vectorised over the masks)."""
+    zs = np.asarray(zs, dtype=np.int64)
+    out = []
+    for fcl in fragment_clbits:
+        loc = np.zeros(zs.shape, dtype=np.int64)
+        for i, c in enumerate(fcl):
+            loc |= ((zs >> np.int64(c)) & 1) << np.int64(i)
+        out.append(loc)
+    return out
+
+
+def wht_pass_bits(m: int, tile_bits: int = 13, later_bits: int = 9) -> list:
+    """The index bits each pass of ``qk_wht_rows`` transforms (qknit_wht.hip: wh_schedule): the low
+    ``min(m, 13)`` in pass 0, the rest spread evenly over ``ceil((m - 13) / 9)`` strided passes."""
+    t0 = min(m, tile_bits)
+    rem = m - t0
+    later = -(-rem // later_bits)
+    return [t0] + [rem // later + (1 if i < rem % later else 0) for i in range(later)]
+
+
+def wht_host(src, m: int) -> np.ndarray:
+    """numpy model of ``qk_wht_rows``: ``out[..., z] = sum_{x < 2^m} (-1)^popcount(x & z) src[..., x]``,
+    unnormalised, by ``m`` levels of butterflies ``(a, b) -> (a + b, a - b)`` with ``a`` the element whose
+    bit is clear, lowest bit first, in the dtype of ``src`` (the kernel takes the bits in another fixed
+    order: equal for exactly representable sums, equal to rounding otherwise)."""
+    src = np.asarray(src)
+    n = 1 << m
+    if src.shape[-1] < n:
+        raise ValueError(f"{src.shape[-1]} columns for m = {m}")
+    x = np.array(src[..., :n], copy=True, order="C")
+    lead = x.shape[:-1]
+    for b in range(m):
+        y = x.reshape(*lead, n >> (b + 1), 2, 1 << b)
+        a = y[..., 0, :].copy()
+        y[..., 0, :] += y[..., 1, :]
+        np.subtract(a, y[..., 1, :], out=y[..., 1, :])
+    return x
+
+
 def key_positions(clbits: list, fragment_clbits: list) -> tuple:
     """For keys whose bit ``i`` is ``clbits[i]``: per fragment ``(keep, where)``, its local ``keep_mask``
     (as :func:`split_clbits`) and, for its kept local bits in ascending order, their bit of the key."""
@@ -213,6 +280,7 @@ class KnitReducer:
         self.qs = [engine.sweep_fragment(ctx, fs).contiguous() for fs in self.frags]
         self.ops = engine.knit_operands(virt, self.frags, self.factored)
         self.clbits = [list(c) for c in self.ops.clbits]
+        self._spectrum = None  # z_spectrum(): formed on first use
         if not self.frags:  # no fragment at all: the knit is the sum of the coefficients at key 0
             vg = [v.operation for v in virt.vgate_instructions]
             self._scalar = float(LabelSpace([g.num_instantiations for g in vg],
@@ -248,9 +316,17 @@ class KnitReducer:
         mats = self._operands(keep, [[0]] * len(keep))
         return _user_order(engine.torch(), self._contract(mats, positions, len(cl)), cl)
 
-    def expectation(self, masks) -> np.ndarray:
+    def expectation(self, masks, *, method: str = "reduce") -> np.ndarray:
         """float64 ``[M]``: ``sum_key (-1)^popcount(key & mask) R[key]`` of the exact quasi-distribution
-        (no projection onto the probability simplex) per mask; see :func:`parse_masks`."""
+        (no projection onto the probability simplex) per mask; see :func:`parse_masks`.
+        ``method="reduce"``: one ``qk_reduce_bits`` pass over the swept rows per batch of masks.
+        ``method="spectrum"``: a gather from :meth:`z_spectrum` (formed once per reducer), for many masks;
+        ``masks`` may then also be an integer numpy array or an int64 tensor (:func:`masks_array`). The
+        two agree to rounding, not bit for bit."""
+        if method == "spectrum":
+            return self._expectation_spectrum(masks)
+        if method != "reduce":
+            raise ValueError(f"method must be 'reduce' or 'spectrum', not {method!r}")
         self.ctx.bind_stream()
         zs = parse_masks(masks, self.N)
         if not zs:
@@ -263,6 +339,81 @@ class KnitReducer:
         for a in mats[1:]:
             prod = prod * a
         return prod.sum(0).cpu().numpy()
+
+    # -- all Z strings: the Walsh-Hadamard spectrum ---------------------------------------------
+    def z_spectrum(self) -> list:
+        """Per fragment the device tensor ``H_f [terms, 2^m_f]``: the Walsh-Hadamard transform
+        (``qk_wht_rows``) of its unreduced operand ``X_f``, so ``H_f[k][z] = sum_x (-1)^popcount(x & z)
+        X_f[k][x]`` is the fragment's factor of every Z string at once. Formed on first use and kept:
+        later calls return the same tensors (as much memory as the operands themselves; treat them as
+        read-only). A dropped fragment is an ``m = 0`` factor; no fragment at all gives ``[]``."""
+        if self._spectrum is None:
+            self.ctx.bind_stream()
+            mats = engine.fragment_operands(self.ctx, self.ops, self.qs) if self.frags else []
+            # the operands are fresh tensors: transform them where they are
+            self._spectrum = [engine.wht_rows(self.ctx, X, len(fcl), out=X) for X, fcl in zip(mats, self.clbits)]
+        return self._spectrum
+
+    def _spectrum_chunks(self, zs: np.ndarray):
+        """``(start, device float64 [n])`` per chunk of ``SPECTRUM_GATHER_CHUNK`` masks: the product over
+        fragments of ``H_f[:, z_f]``, summed over the terms by a fixed tree of elementwise adds (a mask's
+        value does not depend on the chunk it falls in)."""
+        T = engine.torch()
+        dev = T.device("cuda", self.device)
+        H = self.z_spectrum()
+        local = split_masks_array(zs, self.clbits)
+        for s in range(0, len(zs), SPECTRUM_GATHER_CHUNK):
+            prod = None
+            for Hf, lf in zip(H, local):
+                g = Hf.index_select(1, T.from_numpy(lf[s:s + SPECTRUM_GATHER_CHUNK]).to(dev))
+                prod = g if prod is None else prod.mul_(g)
+            while prod.shape[0] > 1:  # rows k and k + ceil(K / 2), level by level
+                h = (prod.shape[0] + 1) // 2
+                prod[:prod.shape[0] - h] += prod[h:]
+                prod = prod[:h]
+            yield s, prod[0]
+
+    def _expectation_spectrum(self, masks) -> np.ndarray:
+        self.ctx.bind_stream()
+        zs = masks_array(masks, self.N)
+        if not self.frags:
+            return np.full(len(zs), self._scalar) if len(zs) else np.zeros(0)
+        out = np.zeros(len(zs))
+        for s, vals in self._spectrum_chunks(zs):
+            out[s:s + vals.numel()] = vals.cpu().numpy()
+        return out
+
+    def expectation_sum(self, masks, weights) -> float:
+        """``sum_j weights[j] <Z_masks[j]>`` by the spectrum route (a cost function of many Z terms):
+        the per-mask values never leave the device, only the sum does."""
+        self.ctx.bind_stream()
+        T = engine.torch()
+        zs = masks_array(masks, self.N)
+        w = np.ascontiguousarray(np.asarray(weights.cpu() if hasattr(weights, "cpu") else weights, dtype=np.float64))
+        if w.ndim != 1 or len(w) != len(zs):
+            raise ValueError(f"{len(zs)} masks but weights of shape {w.shape}")
+        if not len(zs):
+            return 0.0
+        if not self.frags:
+            return float(self._scalar * w.sum())
+        dev = T.device("cuda", self.device)
+        acc = T.zeros((), dtype=T.float64, device=dev)
+        for s, vals in self._spectrum_chunks(zs):
+            acc += T.dot(vals, T.from_numpy(w[s:s + vals.numel()]).to(dev))
+        return float(acc)
+
+    def correlations(self, clbits=None) -> np.ndarray:
+        """numpy ``[k, k]``: entry ``(i, j)`` is ``<Z_clbits[i] Z_clbits[j]>``, the diagonal ``<Z_clbits[i]>``;
+        symmetric. ``None``: all clbits. The ``k (k + 1) / 2`` strings go through the spectrum route."""
+        cl = list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+        k = len(cl)
+        iu, ju = np.triu_indices(k)
+        bit = np.left_shift(np.int64(1), np.asarray(cl, dtype=np.int64))
+        vals = self._expectation_spectrum(bit[iu] | bit[ju])
+        out = np.zeros((k, k))
+        out[iu, ju] = vals
+        out[ju, iu] = vals
+        return out
 
     def sample(self, shots: int, seed: int = 0, clbits=None):
         """``shots`` measurement outcomes of the exact knit: device int64 ``[shots]`` of keys in draw

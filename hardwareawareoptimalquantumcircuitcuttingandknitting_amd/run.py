@@ -538,15 +538,24 @@ def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 
 
 
 def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device: int = 0,
-                                    factored: bool | None = None, group=None, sample: bool = False):
+                                    factored: bool | None = None, group=None, sample: bool = False,
+                                    weights=None, method: str = "reduce"):
     """Expectation values of Pauli-Z strings on the exact knit (the quasi-distribution itself, no
     projection): ``sum_key (-1)^popcount(key & mask) R[key]`` per observable, without the 2^N output.
     ``observables``: int masks over the clbits, or ``'ZIIZ'`` strings (rightmost character = clbit 0,
     one character per clbit). Returns ``(float64 [M], RunTimeInfo)``; the sweep is ``run_time``,
-    reduce + combine ``knit_time``. Same restrictions as :func:`run_virtual_circuit_marginal`."""
+    reduce + combine ``knit_time``. Same restrictions as :func:`run_virtual_circuit_marginal`.
+
+    ``method="spectrum"`` answers from the fragments' Walsh-Hadamard spectra
+    (:meth:`observables.KnitReducer.z_spectrum`): one transform, then a gather per mask, the route for
+    thousands of strings and more; the masks may then be an integer numpy array or an int64 tensor.
+    ``weights`` (one per observable): the result is the float ``sum_j weights[j] <Z_j>`` instead, always
+    by the spectrum route."""
+    if method not in ("reduce", "spectrum"):
+        raise ValueError(f"method must be 'reduce' or 'spectrum', not {method!r}")
     red, run_time = _reducer(virt, device, factored, group, sample)
     now = perf_counter()
-    vals = red.expectation(observables)
+    vals = red.expectation(observables, method=method) if weights is None else red.expectation_sum(observables, weights)
     info = RunTimeInfo(run_time, perf_counter() - now)
     log.info("Knitted in %.2fs.", info.knit_time)
     return vals, info

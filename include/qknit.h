@@ -503,6 +503,18 @@ int qk_reduce_bits(qk_ctx* ctx, int64_t rows, int m, const double* src, int64_t 
                    int64_t n_flips, const uint64_t* flip_masks, double* dst, int64_t ld_dst, void* work,
                    int64_t work_bytes);
 
+/* ---- row-wise Walsh-Hadamard transform (qknit_wht.hip): every Z-string parity of the rows at once ---
+ * dst[r * ld_dst + z] = sum over x in [0, 2^m) of (-1)^popcount(x & z) * src[r * ld_src + x]
+ * for r < rows, z < 2^m; unnormalised (applied twice it gives 2^m times the rows). 0 <= m <= 30;
+ * ld_src, ld_dst >= 2^m (columns of dst at and beyond 2^m are not written); rows may start at any
+ * 8-byte offset. src == dst with ld_src == ld_dst transforms in place; any other overlap of the two
+ * row ranges is refused. rows == 0 is a no-op. src / dst are DEVICE pointers; no workspace: one pass
+ * for m <= 13, two for m <= 22, three beyond, each reading and writing every element once (the later
+ * ones in place on dst). Deterministic: no atomics, every output the root of a radix-2 add / sub tree
+ * of depth m whose shape depends on m alone, so a row's result does not depend on the other rows, and
+ * the in-place and out-of-place forms agree bit for bit. */
+int qk_wht_rows(qk_ctx* ctx, int64_t rows, int m, const double* src, int64_t ld_src, double* dst, int64_t ld_dst);
+
 /* ---- draws from rows of a product that is never stored (qknit_shots.hip): shots from the knit ---
  * u[i] = u(seed, label, first + i) for i < n: the counter-based stream of qk_sample_counts (DEVICE u). */
 int qk_uniforms(qk_ctx* ctx, uint64_t seed, int64_t label, int64_t first, int64_t n, double* u);

@@ -13,7 +13,13 @@ operands), beside the only other route to the same thing in the same process: th
 torch.cumsum over its 2^32 output and torch.searchsorted of the same number of targets. The three
 kernels of qk_sample_rows are timed separately from a kernel trace of a child process
 (``rocprofv3 --kernel-trace -- python tools/obs_bench.py --shots-child``): per sample() call the sum of
-each kernel's dispatches, median over the calls."""
+each kernel's dispatches, median over the calls.
+
+``--spectrum`` runs the all-Z-strings leg instead (``--out``: e.g. profiles/obs_bench_spectrum.json):
+qk_wht_rows alone on [64, 2^16] and [256, 2^16] with its achieved bytes/s, the one-off cost of
+KnitReducer.z_spectrum(), expectation(method="spectrum") for 16 to 2^20 masks beside the unchanged
+expectation(method="reduce") for 16, 64 and 1024, and the smallest measured M at which the spectrum
+route with its one-off cost wins."""
 import argparse
 import glob
 import json
@@ -151,8 +157,69 @@ def shots_leg(args):
             fh.write("\n")
 
 
+def spectrum_leg(args):
+    """All Z strings at once (``--out``: e.g. profiles/obs_bench_spectrum.json): qk_wht_rows alone, the
+    one-off cost of KnitReducer.z_spectrum(), and expectation(method="spectrum") beside the unchanged
+    expectation(method="reduce") of the same reducer in the same process."""
+    import numpy as np
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine, observables as ob
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+
+    res = {"config": "syc_32_5_p2", "device": torch.cuda.get_device_name(0), "reps": 20}
+    _, cut, _ = cutting.config_cut_circuit("syc", 32, 5, 2)
+    red = KnitReducer(VirtualCircuit(cut))
+    ctx = engine.get_context(0)
+    res["fragments"] = [{"rows": int(q.shape[0]), "m": len(cl)} for q, cl in zip(red.qs, red.clbits)]
+    res["terms"] = int(red.ops.num_terms)
+
+    kernel = {}
+    m = 16
+    passes = len(ob.wht_pass_bits(m))
+    for rows in (64, 256):
+        src = torch.randn((rows, 1 << m), dtype=torch.float64, device="cuda")
+        dst = torch.empty_like(src)
+        for name, fn in (("out_of_place", lambda: engine.wht_rows(ctx, src, m, out=dst)),
+                         ("in_place", lambda: engine.wht_rows(ctx, dst, m, out=dst))):
+            t = timed(torch, fn)
+            t["bytes_moved"] = 2 * passes * rows * (1 << m) * 8
+            t["GBs"] = t["bytes_moved"] / t["median_ms"] / 1e6
+            kernel[f"rows_{rows}_{name}"] = t
+    res["qk_wht_rows"] = {"m": m, "passes": passes, "pass_bits": ob.wht_pass_bits(m), **kernel}
+
+    def spectrum_once():
+        red._spectrum = None
+        return red.z_spectrum()
+
+    res["z_spectrum_once"] = timed(torch, spectrum_once)
+    res["z_spectrum_bytes"] = int(sum(h.numel() * 8 for h in red.z_spectrum()))
+    rng = np.random.default_rng(0)
+    masks = rng.integers(0, 1 << 32, size=1 << 20, dtype=np.int64)
+    for M in (16, 64, 1024, 1 << 17, 1 << 20):
+        res[f"spectrum_{M}"] = timed(torch, lambda: red.expectation(masks[:M], method="spectrum"))
+    for M in (16, 64, 1024):
+        zs = masks[:M].tolist()
+        res[f"reduce_{M}"] = timed(torch, lambda: red.expectation(zs, method="reduce"))
+    res["check"] = {"spectrum_vs_reduce_max_abs_diff_1024": float(abs(
+        red.expectation(masks[:1024], method="spectrum") - red.expectation(masks[:1024].tolist())).max())}
+    w = rng.standard_normal(1 << 20)
+    res["expectation_sum_2^20"] = timed(torch, lambda: red.expectation_sum(masks, w))
+    once = res["z_spectrum_once"]["median_ms"]
+    wins = [M for M in (16, 64, 1024) if res[f"spectrum_{M}"]["median_ms"] + once < res[f"reduce_{M}"]["median_ms"]]
+    res["crossover"] = {"smallest_measured_M_where_spectrum_plus_once_beats_reduce": wins[0] if wins else None,
+                        "measured_M": [16, 64, 1024]}
+    print(json.dumps(res, indent=1), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--spectrum", action="store_true", help="the Walsh-Hadamard spectrum leg only (see spectrum_leg)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-dense", action="store_true", help="skip the dense route (needs 34 GB for the output)")
     ap.add_argument("--shots", action="store_true", help="the shots leg only (see the module docstring)")
@@ -162,6 +229,8 @@ def main():
         return shots_child()
     if args.shots:
         return shots_leg(args)
+    if args.spectrum:
+        return spectrum_leg(args)
     import torch
 
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
