@@ -28,7 +28,8 @@ from .virtual_gates import (
 )
 from .virtual_circuit import VirtualCircuit, generate_instantiations
 from .run import (RunTimeInfo, run_virtual_circuit, run_virtual_circuit_dense, run_virtual_circuit_expectation,
-                  run_virtual_circuit_marginal, run_virtual_circuit_shots)
+                  run_virtual_circuit_marginal, run_virtual_circuit_probabilities, run_virtual_circuit_shots,
+                  run_virtual_circuit_xeb)
 
 __all__ = [
     "ClassicalRegister", "QuantumCircuit", "QuantumRegister", "QuasiDistr", "RZZ_ACCURACY",
@@ -36,4 +37,5 @@ __all__ = [
     "VirtualCZ", "VirtualGateEndpoint", "VirtualMove", "VirtualRZZ", "WireCut", "VirtualCircuit",
     "generate_instantiations", "RunTimeInfo", "run_virtual_circuit", "run_virtual_circuit_dense",
     "run_virtual_circuit_marginal", "run_virtual_circuit_expectation", "run_virtual_circuit_shots",
+    "run_virtual_circuit_probabilities", "run_virtual_circuit_xeb",
 ]

@@ -734,6 +734,92 @@ def wht_rows(ctx: Context, src, m: int | None = None, out=None):
     return out
 
 
+KNIT_AT_MAX_FRAGMENTS = 16  # QK_KNIT_AT_MAX_FRAGMENTS
+
+
+def transpose_rows(ctx: Context, X, m: int | None = None, out=None):
+    """``qk_transpose_rows``: ``out[x, k] = X[k, x]`` for ``k < K``, ``x < 2^m`` and exactly 0.0 in the pad
+    columns ``K <= k < ldt`` -> contiguous ``[2^m, ldt]``, ``ldt`` = K rounded up to a multiple of 16 (the
+    operand layout of :func:`knit_at`). ``X``: float64 ``[K >= 1, >= 2^m]`` with unit column stride, only
+    read; ``m`` defaults to its column count, which must then be a power of two. ``out`` (optional): a
+    contiguous float64 ``[2^m, ldt]`` on the device of ``X`` that does not overlap it."""
+    T = torch()
+    if X.dim() != 2 or X.dtype != T.float64 or X.shape[0] < 1 or (X.shape[1] > 1 and X.stride(1) != 1) or not X.is_cuda:
+        raise ValueError("X must be a device float64 [K >= 1, >= 2^m] with unit column stride")
+    K = X.shape[0]
+    if m is None:
+        cols = X.shape[1]
+        if cols < 1 or cols & (cols - 1):
+            raise ValueError(f"X has {cols} columns, not a power of two: pass m")
+        m = cols.bit_length() - 1
+    m = int(m)
+    if not 0 <= m <= 30:
+        raise ValueError(f"m must be in 0..30, not {m}")
+    n = 1 << m
+    if X.shape[1] < n:
+        raise ValueError(f"X has {X.shape[1]} columns for m = {m}")
+    ldx = X.stride(0) if K > 1 else max(X.stride(0), n)
+    if ldx < n:
+        raise ValueError(f"row stride below 2^m = {n}")
+    ldt = -(-K // 16) * 16
+    if out is None:
+        out = T.empty((n, ldt), dtype=T.float64, device=X.device)
+    if out.dtype != T.float64 or tuple(out.shape) != (n, ldt) or not out.is_contiguous() or out.device != X.device:
+        raise ValueError(f"out must be a contiguous float64 [{n}, {ldt}] on the device of X")
+    s0, d0 = X.data_ptr(), out.data_ptr()
+    if s0 < d0 + n * ldt * 8 and d0 < s0 + ((K - 1) * ldx + n) * 8:
+        raise ValueError("X and out overlap")
+    ctx.check(ctx.lib.qk_transpose_rows(ctx.handle, K, m, X.data_ptr(), ldx, out.data_ptr(), ldt), "qk_transpose_rows")
+    return out
+
+
+def knit_at(ctx: Context, Xts: list, positions: list, keys, dead: int = 0, out=None):
+    """``qk_knit_at``: ``out[j] = sum_k prod_f Xts[f][x_f(j), k]`` with bit ``i`` of ``x_f(j)`` = bit
+    ``positions[f][i]`` of ``keys[j]``, and exactly 0.0 where ``keys[j] & dead`` -> float64 ``[n]``.
+    ``Xts``: 1..16 contiguous float64 ``[2^m_f, ldt]`` from :func:`transpose_rows`, all of one ``ldt`` and
+    one device; ``positions[f]``: ``m_f`` key bits in 0..62, any order; ``keys``: contiguous int64 ``[n]`` on
+    that device. Everything but ``out`` is only read."""
+    T = torch()
+    F = len(Xts)
+    if not 1 <= F <= KNIT_AT_MAX_FRAGMENTS:
+        raise ValueError(f"{F} fragments: qk_knit_at takes 1..{KNIT_AT_MAX_FRAGMENTS}")
+    if len(positions) != F:
+        raise ValueError(f"{F} operands but {len(positions)} position tables")
+    positions = [[int(b) for b in pos] for pos in positions]
+    dev, ldt = Xts[0].device, Xts[0].shape[-1] if Xts[0].dim() == 2 else -1
+    for Xt, pos in zip(Xts, positions):
+        if Xt.dim() != 2 or Xt.dtype != T.float64 or not Xt.is_contiguous() or not Xt.is_cuda or Xt.device != dev:
+            raise ValueError("every operand must be a contiguous float64 [2^m, ldt] on one HIP device")
+        if Xt.shape[1] != ldt or ldt < 16 or ldt % 16:
+            raise ValueError("the operands must share one ldt, a multiple of 16 (transpose_rows)")
+        if not 0 <= len(pos) <= 30 or Xt.shape[0] != 1 << len(pos):
+            raise ValueError(f"an operand of {Xt.shape[0]} rows for {len(pos)} positions")
+        if any(not 0 <= b <= 62 for b in pos) or len(set(pos)) != len(pos):
+            raise ValueError(f"positions {pos}: distinct key bits in 0..62")
+    flat = [b for pos in positions for b in pos]
+    if len(flat) > 62 or len(set(flat)) != len(flat):
+        raise ValueError("the position tables must be disjoint and hold at most 62 bits")
+    dead = int(dead)
+    if dead < 0 or dead >> 63:
+        raise ValueError(f"dead {dead:#x} outside the 63 key bits")
+    if keys.dtype != T.int64 or keys.dim() != 1 or not keys.is_contiguous() or keys.device != dev:
+        raise ValueError("keys must be a contiguous int64 [n] on the device of the operands")
+    n = keys.numel()
+    if out is None:
+        out = T.empty(n, dtype=T.float64, device=dev)
+    if out.dtype != T.float64 or out.dim() != 1 or out.numel() != n or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous float64 [n] on the device of the operands")
+    if n == 0:
+        return out
+    ptrs = (ctypes.c_void_p * F)(*[Xt.data_ptr() for Xt in Xts])
+    ms = (ctypes.c_int * F)(*[len(pos) for pos in positions])
+    ps = (ctypes.c_int * max(len(flat), 1))(*flat)
+    # K = ldt: the pad columns are zeros, so the entry's K only bounds ldt
+    ctx.check(ctx.lib.qk_knit_at(ctx.handle, F, ldt, ldt, ptrs, ms, ps, keys.data_ptr(), n, dead, out.data_ptr()),
+              "qk_knit_at")
+    return out
+
+
 # ----------------------------------------------------------------------------- shot sampling
 _SEED_STRIDE = 0x632BE59BD9B4E019  # per-fragment stream offset (mirrored by oracle/sampling.py)
 _U64 = (1 << 64) - 1

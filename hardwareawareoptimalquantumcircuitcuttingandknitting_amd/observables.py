@@ -19,6 +19,11 @@ transform, ``H_f[k][z] = sum_x (-1)^popcount(x & z) X_f[k][x]`` (``qk_wht_rows``
 then any number of masks is a gather (``expectation(method="spectrum")``, ``expectation_sum``,
 ``correlations``).
 
+The knit at chosen keys is a gather as well: with each operand transposed once (``qk_transpose_rows``,
+csrc/qknit_lookup.hip) the factors a key takes from a fragment are one contiguous row, and ``qk_knit_at``
+sums their products over the terms: :meth:`KnitReducer.probabilities`, ``linear_xeb``,
+``fidelity_to_counts``, and ``expectation(method="fused")`` on the transposed spectrum.
+
 It builds on the direct path (``engine.prepare_fragments`` / ``sweep_fragment`` / ``knit_operands``
 / ``fragment_operands`` / ``contract``, as ``run._direct_dense``), not on the cached
 ``KnitPipeline``: the pipeline's row pruning rests on a per-entry bound on ``R`` and a marginal sums
@@ -247,6 +252,67 @@ def deposit_bits(keys, x, where: list):
     return keys
 
 
+def extract_bits(keys, where: list):
+    """The inverse of :func:`deposit_bits`: bit ``i`` of the result is bit ``where[i]`` of ``keys`` (integer
+    arrays or tensors alike)."""
+    x = keys & 0
+    for i, b in enumerate(where):
+        x = x | (((keys >> b) & 1) << i)
+    return x
+
+
+def keys_array(keys, n_bits: int):
+    """Outcome keys as a one-dimensional ``int64`` array ``[M]`` with every key in ``0 .. 2^n_bits - 1``. Ints,
+    lists of ints and integer numpy arrays give a numpy array; a torch int64 tensor stays a tensor on its
+    device and is range-checked there (one min / max sync). ``ValueError`` for a key outside the range, a
+    non-integer dtype or more than one dimension."""
+    def outside(lo, hi):
+        if lo < 0 or hi >> n_bits:
+            raise ValueError(f"key {hi if lo >= 0 else lo:#x} outside 0..2^{n_bits} - 1")
+
+    if type(keys).__module__.split(".")[0] == "torch":
+        import torch as T
+
+        if keys.dtype != T.int64:
+            raise ValueError(f"a key tensor must hold int64, not {keys.dtype}")
+        if keys.dim() > 1:
+            raise ValueError(f"a key tensor must be one-dimensional, not {tuple(keys.shape)}")
+        ks = keys.detach().reshape(-1).contiguous()
+        if ks.numel():
+            lo, hi = T.aminmax(ks)
+            outside(int(lo), int(hi))
+        return ks
+    if isinstance(keys, (int, np.integer)):
+        keys = [keys]
+    if not isinstance(keys, np.ndarray):
+        keys = list(keys)
+        if not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in keys):
+            raise ValueError("keys must be integers")
+        if keys:
+            outside(min(int(k) for k in keys), max(int(k) for k in keys))
+        return np.array([int(k) for k in keys], dtype=np.int64).reshape(-1)
+    if keys.dtype.kind not in "iu":
+        raise ValueError(f"a key array must hold integers, not {keys.dtype}")
+    if keys.ndim > 1:
+        raise ValueError(f"a key array must be one-dimensional, not {keys.shape}")
+    if keys.size:
+        outside(int(keys.min()), int(keys.max()))
+    return np.ascontiguousarray(keys.reshape(-1), dtype=np.int64)
+
+
+def knit_at_host(Xs: list, positions: list, keys, dead: int = 0) -> np.ndarray:
+    """numpy model of ``qk_knit_at`` in ``np.longdouble``: ``out[j] = sum_k prod_f Xs[f][k, x_f(j)]`` with bit
+    ``i`` of ``x_f(j)`` = bit ``positions[f][i]`` of ``keys[j]``, and 0 where ``keys[j] & dead``. The operands
+    are taken untransposed, ``[K, 2^m_f]``."""
+    keys = np.asarray(keys, dtype=np.int64).reshape(-1)
+    prod = np.ones((np.asarray(Xs[0]).shape[0], keys.size), dtype=np.longdouble)
+    for X, pos in zip(Xs, positions):
+        prod *= np.asarray(X, dtype=np.longdouble)[:, extract_bits(keys, list(pos))]
+    out = prod.sum(axis=0)
+    out[(keys & np.int64(dead)) != 0] = 0
+    return out
+
+
 def _user_order(T, asc_result, clbits: list):
     """Result indexed with bit i = clbits[i], from the one indexed by the ascending clbits."""
     order = sorted(clbits)
@@ -281,6 +347,8 @@ class KnitReducer:
         self.ops = engine.knit_operands(virt, self.frags, self.factored)
         self.clbits = [list(c) for c in self.ops.clbits]
         self._spectrum = None  # z_spectrum(): formed on first use
+        self._transposed = None  # transposed_operands(): formed on first use
+        self._spectrum_t = None  # the spectrum transposed (expectation(method="fused")): formed on first use
         if not self.frags:  # no fragment at all: the knit is the sum of the coefficients at key 0
             vg = [v.operation for v in virt.vgate_instructions]
             self._scalar = float(LabelSpace([g.num_instantiations for g in vg],
@@ -322,11 +390,16 @@ class KnitReducer:
         ``method="reduce"``: one ``qk_reduce_bits`` pass over the swept rows per batch of masks.
         ``method="spectrum"``: a gather from :meth:`z_spectrum` (formed once per reducer), for many masks;
         ``masks`` may then also be an integer numpy array or an int64 tensor (:func:`masks_array`). The
-        two agree to rounding, not bit for bit."""
+        two agree to rounding, not bit for bit.
+        ``method="fused"``: the same spectrum, read by the lookup kernel (``qk_knit_at`` on a transposed copy
+        of it, formed once and kept; as much memory again): one launch for all masks, the masks being the
+        keys. Masks as for ``"spectrum"``; agrees with it to rounding."""
         if method == "spectrum":
             return self._expectation_spectrum(masks)
+        if method == "fused":
+            return self._expectation_fused(masks)
         if method != "reduce":
-            raise ValueError(f"method must be 'reduce' or 'spectrum', not {method!r}")
+            raise ValueError(f"method must be 'reduce', 'spectrum' or 'fused', not {method!r}")
         self.ctx.bind_stream()
         zs = parse_masks(masks, self.N)
         if not zs:
@@ -458,6 +531,91 @@ class KnitReducer:
             c = c * X[:, x].T
             keys = deposit_bits(keys, x, pos)
         return keys
+
+    # -- the knit at chosen keys ----------------------------------------------------------------
+    def _check_fragment_limit(self) -> None:
+        if len(self.frags) > engine.KNIT_AT_MAX_FRAGMENTS:
+            raise ValueError(f"{len(self.frags)} fragments: the lookup kernel (qk_knit_at) takes at most "
+                             f"{engine.KNIT_AT_MAX_FRAGMENTS}")
+
+    def _device_keys(self, ks):
+        T = engine.torch()
+        dev = T.device("cuda", self.device)
+        return (T.from_numpy(ks) if isinstance(ks, np.ndarray) else ks).to(dev)
+
+    def transposed_operands(self) -> list:
+        """Per fragment the device tensor ``Xt_f [2^m_f, ldt]``: its unreduced operand ``X_f`` transposed
+        (``qk_transpose_rows``; ``ldt`` = the terms rounded up to 16, zero padded), so the factors a key takes
+        from a fragment are one contiguous row. Formed on first use and kept, like :meth:`z_spectrum` (as
+        much memory again as the operands; read-only)."""
+        if self._transposed is None:
+            self.ctx.bind_stream()
+            mats = engine.fragment_operands(self.ctx, self.ops, self.qs) if self.frags else []
+            self._transposed = [engine.transpose_rows(self.ctx, X, len(fcl)) for X, fcl in zip(mats, self.clbits)]
+        return self._transposed
+
+    def probabilities(self, keys, clbits=None):
+        """Device fp64 tensor ``[M]``: the exact knit ``R[key]`` at the given keys (the quasi-distribution
+        itself: no clamp, no projection), without the 2^N output: a gather of one row per fragment and key
+        from the transposed operands (``qk_knit_at``, DESIGN.md §4a "Probabilities at chosen keys").
+        ``keys``: ints, a list, an integer numpy array or an int64 tensor (a device tensor stays on the
+        device; :func:`keys_array`). Bit ``i`` of a key is ``clbits[i]`` (``None``: all clbits, bit i = clbit i);
+        with chosen ``clbits`` the result is the marginal onto them at the keys: the rows are reduced first,
+        as in :meth:`sample`. A key with a bit set on a clbit that no fragment measures has probability 0."""
+        self.ctx.bind_stream()
+        T = engine.torch()
+        cl = list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+        ks = self._device_keys(keys_array(keys, len(cl)))
+        if not self.frags:
+            return (ks == 0).to(T.float64) * self._scalar
+        self._check_fragment_limit()
+        if cl == list(range(self.N)):
+            Xts, where = self.transposed_operands(), self.clbits
+        else:
+            keep, where = key_positions(cl, self.clbits)
+            mats = self._operands(keep, [[0]] * len(keep))
+            Xts = [engine.transpose_rows(self.ctx, X, len(pos)) for X, pos in zip(mats, where)]
+        dead = ((1 << len(cl)) - 1) & ~sum(1 << b for pos in where for b in pos)
+        return engine.knit_at(self.ctx, Xts, where, ks, dead)
+
+    def linear_xeb(self, keys, clbits=None) -> float:
+        """Linear cross-entropy benchmarking score of the sampled ``keys`` against the exact knit:
+        ``D * mean_j R[key_j] - 1`` with ``D = 2^(number of the chosen clbits that some fragment measures)``.
+        The mean is taken on the device; only the scalar leaves it. Arguments as :meth:`probabilities`."""
+        p = self.probabilities(keys, clbits)
+        if not p.numel():
+            raise ValueError("linear_xeb needs at least one key")
+        cl = range(self.N) if clbits is None else clbits
+        measured = {c for fcl in self.clbits for c in fcl}
+        return float(p.mean()) * 2.0 ** sum(1 for c in cl if int(c) in measured) - 1.0
+
+    def fidelity_to_counts(self, counts: dict, clbits=None) -> float:
+        """Hellinger fidelity between the knit and a counts dict ``{key: count}`` (shots of an uncut run or
+        of a device), from the knit at the observed keys alone:
+        ``(sum_key sqrt(max(R[key], 0) * count / shots))^2 / mass`` with ``mass = expectation([0])``. The knit is
+        normalised by its signed total ``mass``, as ``fidelity.hellinger_fidelity`` normalises a dict by the
+        plain sum of its values, not by the total of its clipped entries; the two normalisations differ by
+        the knit's negative mass, which is rounding for exact instances."""
+        T = engine.torch()
+        if not counts:
+            raise ValueError("fidelity_to_counts needs at least one key")
+        p = self.probabilities(list(counts), clbits)
+        c = T.tensor([float(v) for v in counts.values()], dtype=T.float64, device=p.device)
+        mass = float(self.expectation([0])[0])
+        return float((p.clamp(min=0.0) * (c / c.sum())).sqrt().sum()) ** 2 / mass
+
+    def _expectation_fused(self, masks) -> np.ndarray:
+        self.ctx.bind_stream()
+        on_device = type(masks).__module__.split(".")[0] == "torch" and masks.is_cuda
+        ks = keys_array(masks, self.N) if on_device else masks_array(masks, self.N)  # device masks stay there
+        if not self.frags:
+            return np.full(len(ks), self._scalar) if len(ks) else np.zeros(0)
+        self._check_fragment_limit()
+        if self._spectrum_t is None:
+            self._spectrum_t = [engine.transpose_rows(self.ctx, H, len(fcl))
+                                for H, fcl in zip(self.z_spectrum(), self.clbits)]
+        # a Z on a clbit nobody measures is +1: its bit is not read, and no key is dead
+        return engine.knit_at(self.ctx, self._spectrum_t, self.clbits, self._device_keys(ks), 0).cpu().numpy()
 
     def marginal_parity(self, clbits, masks):
         """The mixed form: device fp64 ``[M, 2^k]``, row j the marginal onto ``clbits`` of

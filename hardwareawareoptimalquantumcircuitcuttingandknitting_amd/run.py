@@ -549,10 +549,11 @@ def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device
     ``method="spectrum"`` answers from the fragments' Walsh-Hadamard spectra
     (:meth:`observables.KnitReducer.z_spectrum`): one transform, then a gather per mask, the route for
     thousands of strings and more; the masks may then be an integer numpy array or an int64 tensor.
+    ``method="fused"`` reads the same spectra with the lookup kernel (``qk_knit_at``), one launch for all masks.
     ``weights`` (one per observable): the result is the float ``sum_j weights[j] <Z_j>`` instead, always
     by the spectrum route."""
-    if method not in ("reduce", "spectrum"):
-        raise ValueError(f"method must be 'reduce' or 'spectrum', not {method!r}")
+    if method not in ("reduce", "spectrum", "fused"):
+        raise ValueError(f"method must be 'reduce', 'spectrum' or 'fused', not {method!r}")
     red, run_time = _reducer(virt, device, factored, group, sample)
     now = perf_counter()
     vals = red.expectation(observables, method=method) if weights is None else red.expectation_sum(observables, weights)
@@ -584,3 +585,30 @@ def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed:
     info = RunTimeInfo(run_time, perf_counter() - now)
     log.info("Knitted in %.2fs.", info.knit_time)
     return dict(zip(uniq.tolist(), counts.tolist())), info
+
+
+def run_virtual_circuit_probabilities(virt: VirtualCircuit, keys, *, clbits=None, device: int = 0,
+                                      factored: bool | None = None, group=None, sample: bool = False):
+    """The exact knit at the given outcome keys, i.e. the probabilities of chosen bitstrings (the
+    quasi-distribution itself, no projection), without the 2^N output: one gathered row per fragment and key
+    (:meth:`observables.KnitReducer.probabilities`, ``qk_knit_at``). ``keys``: ints, a list, an integer numpy
+    array or an int64 tensor, e.g. the keys of :func:`run_virtual_circuit_shots`; ``clbits``: the clbits the
+    keys are over (bit ``i`` of a key = ``clbits[i]``), ``None`` = all. Returns ``(float64 numpy [M],
+    RunTimeInfo)``; the sweep is ``run_time``, the lookup ``knit_time``. Same restrictions as
+    :func:`run_virtual_circuit_marginal`."""
+    red, run_time = _reducer(virt, device, factored, group, sample)
+    now = perf_counter()
+    vals = red.probabilities(keys, clbits).cpu().numpy()
+    return vals, RunTimeInfo(run_time, perf_counter() - now)
+
+
+def run_virtual_circuit_xeb(virt: VirtualCircuit, keys, *, clbits=None, device: int = 0,
+                            factored: bool | None = None, group=None, sample: bool = False):
+    """Linear cross-entropy benchmarking score of sampled ``keys`` against the exact knit:
+    ``2^k * mean_j R[key_j] - 1`` over the ``k`` measured clbits (:meth:`observables.KnitReducer.linear_xeb`).
+    Returns ``(float, RunTimeInfo)``; arguments, timing and restrictions as
+    :func:`run_virtual_circuit_probabilities`."""
+    red, run_time = _reducer(virt, device, factored, group, sample)
+    now = perf_counter()
+    score = red.linear_xeb(keys, clbits)
+    return score, RunTimeInfo(run_time, perf_counter() - now)

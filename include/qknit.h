@@ -534,6 +534,27 @@ int qk_sample_rows(qk_ctx* ctx, int64_t K, int m, const double* X, int64_t ldx, 
                    int64_t ldc, const int64_t* draw_off, int64_t n_draws, const double* u, int64_t* x_out,
                    double* w_out, double* row_total, void* work, int64_t work_bytes);
 
+/* ---- the knit at chosen keys (qknit_lookup.hip): probabilities of given bitstrings without the 2^N output ---
+ * qk_transpose_rows: Xt[x * ldt + k] = X[k * ldx + x] for k < K, x < 2^m, and exactly 0.0 for K <= k < ldt:
+ * a key's K factors of one fragment become one contiguous row. K >= 1, 0 <= m <= 30 (m = 0: one row),
+ * ldx >= 2^m, ldt >= K and a multiple of 16 (normally K rounded up). X (only read) and Xt are distinct
+ * DEVICE buffers. A bit-exact permutation.
+ *
+ * qk_knit_at: out[j] = sum_{k<K} prod_{f<F} Xt[f][x_f(j) * ldt + k] for j < n, where bit i of x_f(j) is bit
+ * pos_f[i] of keys[j] (i < m[f]; any order), and out[j] = 0.0 exactly where keys[j] & dead != 0 (`dead`:
+ * the key bits that no fragment measures). 1 <= F <= QK_KNIT_AT_MAX_FRAGMENTS, 0 <= m[f] <= 30 with
+ * sum m[f] <= 62, every position in 0..62, one ldt for all fragments (as above; the pad columns must hold
+ * zeros, as qk_transpose_rows writes them). Xt (F device pointers), m (F ints) and pos (the F position
+ * tables one after the other, sum m[f] ints) are HOST arrays read before the call returns; keys, out and
+ * the operands are DEVICE buffers, keys and operands only read. n == 0 is a no-op.
+ * Deterministic: no atomics; the bits of out[j] depend on keys[j], K, F, ldt and the operands alone, not on
+ * n, j or the other keys: per k the product over f ascending, per lane l < 16 the terms k = l, l + 16, ...
+ * added ascending, the 16 partials combined by an xor butterfly with partners 8, 4, 2, 1. */
+#define QK_KNIT_AT_MAX_FRAGMENTS 16
+int qk_transpose_rows(qk_ctx* ctx, int64_t K, int m, const double* X, int64_t ldx, double* Xt, int64_t ldt);
+int qk_knit_at(qk_ctx* ctx, int F, int64_t K, int64_t ldt, const double* const* Xt, const int* m, const int* pos,
+               const int64_t* keys, int64_t n, uint64_t dead, double* out);
+
 int qk_hellinger(qk_ctx* ctx, int64_t n, const double* p, const double* q, double* acc3);
 
 #ifdef __cplusplus

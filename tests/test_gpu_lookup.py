@@ -1,0 +1,473 @@
+"""Probabilities at chosen keys, on the GPU: ``qk_transpose_rows`` / ``qk_knit_at`` against numpy, and
+``KnitReducer.probabilities`` / ``linear_xeb`` / ``fidelity_to_counts`` / ``expectation(method="fused")`` and the
+``run_virtual_circuit_probabilities`` / ``run_virtual_circuit_xeb`` entry points against the oracle."""
+import ctypes
+import functools
+import random
+
+import numpy as np
+import pytest
+
+import circuits
+import obs_cases
+from oracle import dense, qvm, tables
+from test_observables import np_marginal
+
+from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import (VirtualCircuit, cutting, engine, fidelity,
+                                                                      run_virtual_circuit_expectation,
+                                                                      run_virtual_circuit_probabilities,
+                                                                      run_virtual_circuit_shots, run_virtual_circuit_xeb)
+from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import (KnitReducer, extract_bits,
+                                                                                  knit_at_host)
+
+pytestmark = pytest.mark.gpu
+EPS = 2.0 ** -53
+TOL = 1e-12  # the project's parity tolerance
+
+
+@pytest.fixture(scope="module")
+def T(require_gpu):
+    import torch
+
+    return torch
+
+
+# ----------------------------------------------------------------------------- 1. the transposition
+@pytest.mark.parametrize("m", [0, 1, 5, 10, 13])
+def test_transpose_rows_equals_the_transpose_bit_for_bit(T, m):
+    ctx = engine.get_context(0)
+    W = 1 << m
+    for K in (1, 3, 16, 17, 65):
+        rng = np.random.default_rng(100 * m + K)
+        Xp = np.full((K, W + 3), 1e300)
+        Xp[:, :W] = rng.standard_normal((K, W))
+        Xd = T.from_numpy(Xp).cuda()
+        before = Xd.clone()
+        Xt = engine.transpose_rows(ctx, Xd[:, :W], m)
+        ldt = -(-K // 16) * 16
+        assert tuple(Xt.shape) == (W, ldt) and Xt.is_contiguous() and Xt.dtype == T.float64
+        got = Xt.cpu().numpy()
+        assert got[:, :K].tobytes() == np.ascontiguousarray(Xp[:, :W].T).tobytes(), (K, m)
+        assert not got[:, K:].any() and not np.signbit(got[:, K:]).any(), "pad columns must be +0.0"
+        assert not (got == 1e300).any()
+        assert T.equal(Xd, before), "X was written"
+        # into a buffer of the caller's, prefilled: every element is written
+        out = T.full((W, ldt), 7.0, dtype=T.float64, device="cuda")
+        assert engine.transpose_rows(ctx, Xd[:, :W], m, out=out) is out and T.equal(out, Xt)
+    # m defaults to the column count
+    X = T.from_numpy(rng.standard_normal((5, W))).cuda()
+    assert T.equal(engine.transpose_rows(ctx, X)[:, :5], X.T)
+
+
+# ----------------------------------------------------------------------------- 2. the lookup vs numpy
+def _shape(F, rng):
+    """Bits per fragment, mixed from (0, 1, 5, 13) with at most 62 in all (F = 16: mostly 0-3 each), and
+    shuffled position tables over a shuffled set of key bits with gaps."""
+    if F == 16:
+        ms = [0, 1, 2, 3, 0, 1, 5, 3, 2, 1, 0, 3, 13, 1, 2, 3]
+    else:
+        ms = {1: [13], 2: [13, 5], 3: [5, 0, 13]}[F]
+    rng.shuffle(ms)
+    bits = rng.permutation(62)[:sum(ms)].tolist()
+    positions, at = [], 0
+    for m in ms:
+        positions.append(bits[at:at + m])
+        at += m
+    return ms, positions
+
+
+def _keys(n, positions, rng):
+    used = sum(1 << b for pos in positions for b in pos)
+    keys = rng.integers(0, 1 << 62, size=n, dtype=np.int64) & np.int64(used)
+    for j, k in enumerate((0, used)[:n]):
+        keys[j] = k
+    return keys, used
+
+
+def _device_operands(T, Xs, ms):
+    ctx = engine.get_context(0)
+    return [engine.transpose_rows(ctx, T.from_numpy(np.ascontiguousarray(X)).cuda(), m) for X, m in zip(Xs, ms)]
+
+
+@pytest.mark.parametrize("F", [1, 2, 3, 16])
+def test_knit_at_matches_the_longdouble_model_within_the_derived_band(T, F):
+    """|got - exact| <= (K + F) 2^-53 sum_k prod_f |X_f[k][x_f]|: a product of F factors and a sum of K terms
+    in any order."""
+    ctx = engine.get_context(0)
+    worst = 0.0
+    for K in (1, 3, 16, 17, 65):
+        rng = np.random.default_rng(1000 * F + K)
+        ms, positions = _shape(F, rng)
+        assert sum(ms) <= 62 and len(ms) == F
+        Xs = [rng.standard_normal((K, 1 << m)) for m in ms]
+        Xts = _device_operands(T, Xs, ms)
+        all_keys, used = _keys(4097, positions, rng)
+        exact = knit_at_host(Xs, positions, all_keys)
+        scale = knit_at_host([np.abs(X) for X in Xs], positions, all_keys)
+        for n in (0, 1, 15, 16, 17, 4097):
+            keys = all_keys[:n]
+            got = engine.knit_at(ctx, Xts, positions, T.from_numpy(keys).cuda())
+            assert got.shape == (n,) and got.dtype == T.float64
+            if n == 0:
+                continue
+            err = np.abs(got.cpu().numpy().astype(np.longdouble) - exact[:n])
+            band = (K + F) * EPS * scale[:n]
+            assert np.all(err <= band), (K, n, int(np.argmax(err / band)), float((err / band).max()))
+            worst = max(worst, float((err / band).max()))
+    print(f"F = {F}: worst error {worst:.3g} of the band")
+
+
+@pytest.mark.parametrize("F", [1, 2, 3, 16])
+def test_knit_at_is_exact_on_small_integers(T, F):
+    ctx = engine.get_context(0)
+    for K in (1, 3, 16, 17, 65):
+        rng = np.random.default_rng(2000 * F + K)
+        ms, positions = _shape(F, rng)
+        hi = 2 if F == 16 else 5  # |product| <= 2^16 or 125, |sum| far below 2^53
+        Xs = [rng.integers(-hi, hi + 1, size=(K, 1 << m)) for m in ms]
+        keys, _ = _keys(4097, positions, rng)
+        want = np.ones((K, keys.size), dtype=np.int64)
+        for X, pos in zip(Xs, positions):
+            want *= X[:, extract_bits(keys, pos)]
+        got = engine.knit_at(ctx, _device_operands(T, [X.astype(np.float64) for X in Xs], ms), positions,
+                             T.from_numpy(keys).cuda())
+        assert np.array_equal(got.cpu().numpy(), want.sum(axis=0).astype(np.float64)), K
+
+
+# ----------------------------------------------------------------------------- 3. fixed association
+@pytest.mark.parametrize("F,K", [(2, 65), (3, 17), (16, 16), (1, 3)])
+def test_knit_at_bits_depend_on_the_key_alone(T, F, K):
+    ctx = engine.get_context(0)
+    rng = np.random.default_rng(31 * F + K)
+    ms, positions = _shape(F, rng)
+    Xs = [rng.standard_normal((K, 1 << m)) for m in ms]
+    Xts = _device_operands(T, Xs, ms)
+    before = [x.clone() for x in Xts]
+    keys_h, used = _keys(4097, positions, rng)
+    keys = T.from_numpy(keys_h).cuda()
+    a = engine.knit_at(ctx, Xts, positions, keys)
+    assert T.equal(engine.knit_at(ctx, Xts, positions, keys), a), "two launches differ"
+    perm = T.from_numpy(rng.permutation(4097)).cuda()
+    assert T.equal(engine.knit_at(ctx, Xts, positions, keys[perm].contiguous()), a[perm])
+    assert T.equal(engine.knit_at(ctx, Xts, positions, keys[4096:].contiguous()), a[4096:])  # alone, and last of 4097
+    assert T.equal(engine.knit_at(ctx, Xts, positions, keys[:1].contiguous()), a[:1])
+    dup = T.cat([keys[5:6]] * 40 + [keys[:3], keys[5:6]])
+    got = engine.knit_at(ctx, Xts, positions, dup)
+    assert T.equal(got[:40], a[5:6].expand(40)) and T.equal(got[40:43], a[:3]) and T.equal(got[43:], a[5:6])
+    # a preallocated output; the operands are only read
+    out = T.full((4097,), 7.0, dtype=T.float64, device="cuda")
+    assert engine.knit_at(ctx, Xts, positions, keys, out=out) is out and T.equal(out, a)
+    assert all(T.equal(x, b) for x, b in zip(Xts, before))
+    # dead bits: exactly 0.0 there, the neighbours as before
+    free = [b for b in range(62) if not used >> b & 1][:2]
+    dead = sum(1 << b for b in free)
+    marked = keys.clone()
+    marked[1::3] |= 1 << free[0]
+    marked[2::7] |= 1 << free[1]
+    hit = (marked & dead) != 0
+    assert bool(hit.any()) and not bool(hit.all())
+    got = engine.knit_at(ctx, Xts, positions, marked, dead)
+    assert not got[hit].any() and not T.signbit(got[hit]).any() and T.equal(got[~hit], a[~hit])
+    assert T.equal(engine.knit_at(ctx, Xts, positions, marked), a)  # not dead: those bits are not read
+
+
+def test_lookup_entries_reject_bad_arguments(T):
+    """Every bad argument returns a non-zero status with qk_last_error set, and nothing is launched."""
+    ctx = engine.get_context(0)
+    lib = ctx.lib
+    X = T.ones((2, 4), dtype=T.float64, device="cuda")
+    Xt = T.full((4, 16), -7.0, dtype=T.float64, device="cuda")
+
+    def transpose(K=2, m=2, X_p=X.data_ptr(), ldx=4, Xt_p=Xt.data_ptr(), ldt=16):
+        return lib.qk_transpose_rows(ctx.handle, K, m, X_p, ldx, Xt_p, ldt)
+
+    bad = {"m must be": dict(m=31), "m must be in": dict(m=-1), "K must be": dict(K=0), "ldx": dict(ldx=3),
+           "ldt": dict(ldt=8), "ldt must": dict(ldt=17), "null buffer": dict(X_p=None)}
+    for msg, kw in bad.items():
+        assert transpose(**kw) != 0, kw
+        assert msg.encode() in lib.qk_last_error(ctx.handle), (kw, lib.qk_last_error(ctx.handle))
+    assert transpose(Xt_p=None) != 0 and b"null buffer" in lib.qk_last_error(ctx.handle)
+    assert transpose(K=17) != 0 and b"ldt" in lib.qk_last_error(ctx.handle)
+    T.cuda.synchronize()
+    assert bool((Xt == -7.0).all())  # nothing ran
+    assert transpose() == 0
+    T.cuda.synchronize()
+    assert bool((Xt[:, :2] == 1.0).all()) and not Xt[:, 2:].any()
+
+    A = T.zeros((2, 16), dtype=T.float64, device="cuda")  # [2^1, ldt] for K = 2: ones, zero pad
+    A[:, :2] = 1.0
+    keys = T.tensor([0, 1, 2, 3], device="cuda")
+    out = T.full((4,), -7.0, dtype=T.float64, device="cuda")
+
+    def knit(F=2, K=2, ldt=16, Xt_p=(A.data_ptr(), A.data_ptr()), m=(1, 1), pos=(0, 1), keys_p=keys.data_ptr(), n=4, dead=0,
+             out_p=out.data_ptr()):
+        Xt_a = None if Xt_p is None else (ctypes.c_void_p * len(Xt_p))(*Xt_p)
+        m_a = None if m is None else (ctypes.c_int * len(m))(*m)
+        pos_a = None if pos is None else (ctypes.c_int * len(pos))(*pos)
+        return lib.qk_knit_at(ctx.handle, F, K, ldt, Xt_a, m_a, pos_a, keys_p, n, dead, out_p)
+
+    bad = {"F must be": dict(F=0), "F must be in": dict(F=17), "K must be": dict(K=0), "ldt": dict(ldt=8),
+           "ldt must": dict(ldt=24), "at least K": dict(K=17), "m must be": dict(m=(31, 1)), "m must be in": dict(m=(1, -1)),
+           "position": dict(pos=(0, 63)), "a position": dict(pos=(-1, 1)), "n >= 0": dict(n=-1)}
+    for msg, kw in bad.items():
+        assert knit(**kw) != 0, kw
+        assert msg.encode() in lib.qk_last_error(ctx.handle), (kw, lib.qk_last_error(ctx.handle))
+    for kw in (dict(Xt_p=None), dict(Xt_p=(A.data_ptr(), None)), dict(m=None), dict(pos=None), dict(keys_p=None),
+               dict(out_p=None)):
+        assert knit(**kw) != 0 and b"null buffer" in lib.qk_last_error(ctx.handle), kw
+    assert knit(n=0) == 0 and knit(n=0, keys_p=None, out_p=None) == 0
+    T.cuda.synchronize()
+    assert bool((out == -7.0).all())  # nothing ran
+    assert knit() == 0
+    T.cuda.synchronize()
+    assert out.tolist() == [2.0, 2.0, 2.0, 2.0]
+    # the engine wrapper raises before any launch
+    Xts = [A[:2].contiguous(), A[:2].contiguous()]
+    for kw in (dict(Xts=[]), dict(Xts=Xts * 9, positions=[[0]] * 18), dict(positions=[[0]]), dict(positions=[[0], [0]]),
+               dict(positions=[[0], [63]]), dict(positions=[[0, 1], [2]]), dict(keys=keys.int()), dict(keys=keys.cpu()),
+               dict(keys=keys.view(2, 2)), dict(Xts=[Xts[0], Xts[1].float()]), dict(Xts=[Xts[0], A[:, :8].T]),
+               dict(dead=-1), dict(out=out[:3])):
+        args = dict(Xts=Xts, positions=[[0], [1]], keys=keys)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            engine.knit_at(ctx, args.pop("Xts"), args.pop("positions"), args.pop("keys"), **args)
+    for bad_x in (X.float(), X[0], T.ones((2, 6), dtype=T.float64, device="cuda"), X.cpu()):
+        with pytest.raises(ValueError):
+            engine.transpose_rows(ctx, bad_x)
+    with pytest.raises(ValueError):
+        engine.transpose_rows(ctx, X, m=3)
+    with pytest.raises(ValueError, match="out must be"):
+        engine.transpose_rows(ctx, X, out=Xt[:, :8])
+
+
+# ----------------------------------------------------------------------------- 4. end to end vs oracle
+CASES = {
+    "cx_3cuts": lambda: circuits.two_fragment("cx", 3, 3, n_cuts=3),
+    "cx_wide": lambda: circuits.two_fragment("cx", 7, 6, n_cuts=2, seed=3),
+    "three_wide": lambda: circuits.three_fragment(seed=9, sizes=(5, 4, 3)),
+    "partial": lambda: circuits.partial_measure(),
+    "many_traced": lambda: circuits.many_traced(),
+    "same_fragment": lambda: circuits.same_fragment_cut(),
+    "interleaved": obs_cases.interleaved,
+    "extra_clbit": obs_cases.extra_clbit,
+    "rzz": lambda: circuits.two_fragment("rzz"),
+    "move_gate": lambda: circuits.wire_cut(3, 2, extra_gate_cut=True),
+}
+DIRECT_ONLY = ("same_fragment",)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """(cut circuit, oracle dense knit): built once per module and left unchanged."""
+    _, cut = CASES[name]()
+    ref = dense.run_dense(cut)
+    ref.setflags(write=False)
+    return cut, ref
+
+
+@pytest.mark.parametrize("case,factored", [(c, f) for c in sorted(CASES) for f in (False, True)
+                                           if not (f and c in DIRECT_ONLY)])
+def test_probabilities_of_every_key_match_the_oracle(T, case, factored):
+    cut, ref = _case(case)
+    virt = VirtualCircuit(cut)
+    N = virt.circuit.num_clbits
+    assert N <= 13
+    red = KnitReducer(virt, factored=factored)
+    assert red.factored == factored
+    keys = np.arange(1 << N, dtype=np.int64)
+    got = red.probabilities(keys)
+    assert got.shape == (1 << N,) and got.dtype == T.float64 and got.is_cuda
+    worst = float(np.abs(got.cpu().numpy() - ref).max())
+    print(f"{case} factored={factored}: worst deviation {worst:.3g}")
+    assert worst <= TOL
+    raw = got.cpu().numpy().tobytes()
+    assert red.probabilities(keys.tolist()).cpu().numpy().tobytes() == raw
+    assert red.probabilities(T.from_numpy(keys).cuda()).cpu().numpy().tobytes() == raw
+    assert red.probabilities(T.from_numpy(keys)).cpu().numpy().tobytes() == raw
+    assert red.probabilities(keys, list(range(N))).cpu().numpy().tobytes() == raw
+    assert float(red.probabilities(5)[0]) == float(got[5]) and red.probabilities([]).shape == (0,)
+    with pytest.raises(ValueError, match="outside"):
+        red.probabilities([1 << N])
+    if case == "extra_clbit":
+        assert sorted(c for cl in red.clbits for c in cl) == [0, 2, 4]
+        unmeasured = (keys & 0b01010) != 0
+        assert not got.cpu().numpy()[unmeasured].any() and np.abs(got.cpu().numpy()[~unmeasured]).max() > 0
+
+
+# ----------------------------------------------------------------------------- 5. chosen clbits
+@pytest.mark.parametrize("case", ["cx_wide", "three_wide", "interleaved", "extra_clbit", "partial"])
+def test_probabilities_over_chosen_clbits_are_the_marginal_at_the_keys(T, case):
+    """A set that straddles the cut and a non-ascending order: bit i of a key is clbits[i]. A marginal sums
+    up to 2^N entries, hence the band 2^N * 1e-12."""
+    cut, ref = _case(case)
+    virt = VirtualCircuit(cut)
+    N = virt.circuit.num_clbits
+    red = KnitReducer(virt)
+    fcl = [cl for cl in red.clbits if cl]
+    assert len(fcl) >= 2
+    straddle = sorted({fcl[0][0], fcl[0][-1], fcl[1][0], fcl[-1][-1]})
+    rng = random.Random(len(case))
+    mixed = rng.sample(range(N), min(N, 4))
+    if mixed == sorted(mixed):
+        mixed.reverse()
+    band = 2.0 ** N * TOL
+    for clbits in (straddle, mixed, list(reversed(range(N)))):
+        k = len(clbits)
+        got = red.probabilities(np.arange(1 << k), clbits).cpu().numpy()
+        assert np.abs(got - np_marginal(ref, clbits)).max() <= band, clbits
+        assert np.abs(got - red.marginal(clbits).cpu().numpy()).max() <= band, clbits
+        with pytest.raises(ValueError, match="outside"):
+            red.probabilities([1 << k], clbits)
+    with pytest.raises(ValueError, match="duplicate"):
+        red.probabilities([0], [0, 0])
+    with pytest.raises(ValueError, match="outside"):
+        red.probabilities([0], [N])
+
+
+# ----------------------------------------------------------------------------- 6. XEB and fidelity
+@pytest.mark.parametrize("case", ["cx_wide", "three_wide", "extra_clbit", "rzz"])
+def test_linear_xeb_and_fidelity_to_counts(T, case):
+    cut, ref = _case(case)
+    virt = VirtualCircuit(cut)
+    N = virt.circuit.num_clbits
+    red = KnitReducer(virt)
+    D = 2.0 ** sum(len(cl) for cl in red.clbits)
+    keys = red.sample(2000, 11)
+    xeb = red.linear_xeb(keys)
+    want = D * ref[keys.cpu().numpy()].mean() - 1
+    print(f"{case}: XEB of 2000 shots {xeb:.6f} (oracle {want:.6f})")
+    assert isinstance(xeb, float) and abs(xeb - want) <= D * TOL
+    every = np.arange(1 << N)
+    measured = sum(1 << c for cl in red.clbits for c in cl)
+    once = every[(every & ~measured) == 0]  # D keys; the others are exactly 0 and would only dilute the mean
+    mass = float(red.expectation([0])[0])
+    assert abs(red.linear_xeb(once) - (mass - 1)) <= TOL
+    if D == 1 << N:
+        assert abs(red.linear_xeb(every) - (mass - 1)) <= TOL
+    counts, _ = run_virtual_circuit_shots(virt, 2000, seed=11)
+    fid = red.fidelity_to_counts(counts)
+    want = fidelity.hellinger_fidelity(dict(enumerate(ref.tolist())), counts)
+    print(f"{case}: fidelity to 2000 shots {fid:.6f} (oracle {want:.6f})")
+    assert isinstance(fid, float) and abs(fid - want) <= 2.0 ** N * TOL
+    with pytest.raises(ValueError, match="at least one key"):
+        red.linear_xeb([])
+    with pytest.raises(ValueError, match="at least one key"):
+        red.fidelity_to_counts({})
+    # chosen clbits: the XEB of the marginal
+    clbits = [c for cl in red.clbits for c in cl][::-1][:3]
+    sub = red.sample(500, 4, clbits)
+    want = 2.0 ** len(clbits) * np_marginal(ref, clbits)[sub.cpu().numpy()].mean() - 1
+    assert abs(red.linear_xeb(sub, clbits) - want) <= 2.0 ** N * TOL * 2.0 ** len(clbits)
+
+
+# ----------------------------------------------------------------------------- 7. expectation(method="fused")
+@pytest.mark.parametrize("case", ["cx_wide", "three_wide"])
+def test_fused_expectations_match_the_spectrum_route(T, case):
+    """Both routes evaluate sum_k prod_f H_f[k][z_f], each within (K + F) 2^-53 sum_k prod_f |H_f| of it."""
+    cut, _ = _case(case)
+    virt = VirtualCircuit(cut)
+    N = virt.circuit.num_clbits
+    red = KnitReducer(virt)
+    rng = np.random.default_rng(N)
+    masks = np.concatenate([[0, (1 << N) - 1], rng.integers(0, 1 << N, size=300)]).astype(np.int64)
+    got = red.expectation(masks, method="fused")
+    assert got.shape == masks.shape and got.dtype == np.float64
+    by_spectrum = red.expectation(masks, method="spectrum")
+    H = [h.cpu().numpy() for h in red.z_spectrum()]
+    K, F = H[0].shape[0], len(H)
+    scale = knit_at_host([np.abs(h) for h in H], red.clbits, masks).astype(np.float64)
+    frac = np.abs(got - by_spectrum) / (2 * (K + F) * EPS * scale)
+    print(f"{case}: fused against spectrum, worst {frac.max():.3g} of the band")
+    assert np.all(frac <= 1)
+    for other in (masks.tolist(), T.from_numpy(masks), T.from_numpy(masks).cuda()):
+        assert red.expectation(other, method="fused").tobytes() == got.tobytes()
+    assert red.expectation(masks, method="spectrum").tobytes() == by_spectrum.tobytes()  # the spectrum is left alone
+    vals, info = run_virtual_circuit_expectation(virt, masks, method="fused")
+    assert vals.tobytes() == got.tobytes() and info.run_time > 0 and info.knit_time > 0
+    with pytest.raises(ValueError, match="method"):
+        red.expectation(masks[:2], method="auto")
+    with pytest.raises(ValueError, match="outside"):
+        red.expectation([1 << N], method="fused")
+
+
+# ----------------------------------------------------------------------------- 8. entry points
+def test_probabilities_and_xeb_entry_points(T):
+    cut, ref = _case("cx_wide")
+    virt = VirtualCircuit(cut)
+    red = KnitReducer(virt)
+    keys = red.sample(3000, 9)
+    probs, info = run_virtual_circuit_probabilities(virt, keys)
+    assert isinstance(probs, np.ndarray) and probs.dtype == np.float64 and probs.shape == (3000,)
+    assert probs.tobytes() == red.probabilities(keys).cpu().numpy().tobytes()
+    assert info.run_time > 0 and info.knit_time > 0
+    xeb, info = run_virtual_circuit_xeb(virt, keys)
+    assert isinstance(xeb, float) and xeb == red.linear_xeb(keys) and info.run_time > 0 and info.knit_time > 0
+    sub, _ = run_virtual_circuit_probabilities(virt, np.arange(8), clbits=[12, 0, 6], factored=False)
+    assert sub.tobytes() == KnitReducer(virt, factored=False).probabilities(np.arange(8), [12, 0, 6]).cpu().numpy().tobytes()
+    sx, _ = run_virtual_circuit_xeb(virt, [0, 3, 5], clbits=[12, 0, 6])
+    assert sx == red.linear_xeb([0, 3, 5], [12, 0, 6])
+    for entry in (run_virtual_circuit_probabilities, run_virtual_circuit_xeb):
+        with pytest.raises(ValueError, match="exact"):
+            entry(virt, [0], sample=True)
+        with pytest.raises(ValueError, match="one GPU"):
+            entry(virt, [0], group="WORLD")
+
+    class Foreign:
+        def run(self, circuits, shots=None):
+            raise AssertionError("not reached")
+
+    virt.set_backend([f for f in virt.fragment_circuits if len(f)][0], Foreign())
+    for entry in (run_virtual_circuit_probabilities, run_virtual_circuit_xeb):
+        with pytest.raises(ValueError, match="MI355X backend"):
+            entry(virt, [0])
+
+
+def test_no_fragment_at_all_puts_the_scalar_on_key_zero(T):
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.circuit import (ClassicalRegister, QuantumCircuit,
+                                                                                  QuantumRegister)
+
+    red = KnitReducer(VirtualCircuit(QuantumCircuit(QuantumRegister(0, "q"), ClassicalRegister(3, "c"))))
+    assert not red.frags
+    assert red.probabilities([0, 1, 7, 0]).tolist() == [red._scalar, 0.0, 0.0, red._scalar]
+    assert red.expectation([0, 5], method="fused").tolist() == [red._scalar] * 2
+
+
+def test_more_than_sixteen_fragments_are_refused(T, monkeypatch):
+    cut, _ = _case("rzz")
+    red = KnitReducer(VirtualCircuit(cut))
+    monkeypatch.setattr(engine, "KNIT_AT_MAX_FRAGMENTS", 1)
+    with pytest.raises(ValueError, match="at most 1"):
+        red.probabilities([0])
+    with pytest.raises(ValueError, match="at most 1"):
+        red.expectation([0], method="fused")
+
+
+# ----------------------------------------------------------------------------- 9. wide output
+@pytest.mark.slow
+def test_wide_output_36_clbits_probabilities_of_drawn_keys(T):
+    """hwe 36 in two 18-qubit fragments: the probabilities of keys no 2^N buffer could index, against the
+    oracle's per-fragment rows and coefficients; peak memory far below any such buffer."""
+    _, cut, _ = cutting.config_cut_circuit("hwe", 36, 1, 2)
+    view = qvm.CutView(cut)
+    (kind, params, _, _), = view.vgates
+    coef = np.asarray(tables.coefficients(kind, params))
+    rows = [dense.fragment_q(view, list(qreg)) for qreg in view.qregs if len(qreg)]
+    assert [len(cl) for _, cl in rows] == [18, 18] and all(q.shape[0] == coef.size for q, _ in rows)
+    (q0, cl0), (q1, cl1) = rows
+
+    virt = VirtualCircuit(cut)
+    T.cuda.synchronize()
+    T.cuda.reset_peak_memory_stats()
+    keys, _ = run_virtual_circuit_shots(virt, 4096, seed=36, memory=True)
+    probs, info = run_virtual_circuit_probabilities(virt, keys[:256])
+    xeb, _ = run_virtual_circuit_xeb(virt, keys)
+    T.cuda.synchronize()
+    peak = T.cuda.max_memory_allocated()
+    print(f"peak device memory {peak / 2**20:.1f} MiB, sweep {info.run_time * 1e3:.1f} ms, lookup "
+          f"{info.knit_time * 1e3:.1f} ms, XEB of 4096 shots {xeb:.4f}")
+    assert peak < 4 << 30
+    keys = keys.cpu().numpy()[:256]
+    assert [list(c) for c in KnitReducer(virt).clbits] == [list(cl0), list(cl1)]
+    x0, x1 = extract_bits(keys, list(cl0)), extract_bits(keys, list(cl1))
+    want = ((coef[:, None] * q0[:, x0]) * q1[:, x1]).sum(axis=0)
+    assert np.abs(probs - want).max() <= TOL

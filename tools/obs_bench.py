@@ -19,7 +19,10 @@ each kernel's dispatches, median over the calls.
 qk_wht_rows alone on [64, 2^16] and [256, 2^16] with its achieved bytes/s, the one-off cost of
 KnitReducer.z_spectrum(), expectation(method="spectrum") for 16 to 2^20 masks beside the unchanged
 expectation(method="reduce") for 16, 64 and 1024, and the smallest measured M at which the spectrum
-route with its one-off cost wins."""
+route with its one-off cost wins.
+
+``--lookup`` runs the probabilities-at-chosen-keys leg instead (``--out``: e.g.
+profiles/obs_bench_lookup.json): see lookup_leg."""
 import argparse
 import glob
 import json
@@ -217,8 +220,95 @@ def spectrum_leg(args):
             fh.write("\n")
 
 
+def lookup_leg(args):
+    """Probabilities at chosen keys (``--out``: e.g. profiles/obs_bench_lookup.json): for M = 2^10, 2^17, 2^20
+    uniformly random keys KnitReducer.probabilities, qk_knit_at alone with its achieved bytes/s against
+    M * sum_f 8 * ldt bytes, qk_transpose_rows alone, the one-off cost of the transposed operands, and beside
+    them in the same process the torch gather route on the same operands (index_select + product + tree,
+    KnitReducer._spectrum_chunks applied to X_f), and expectation(method="spectrum") against method="fused" on
+    the same masks. At M = 2^10 the dense route as well: run_virtual_circuit_dense(...)[keys]."""
+    import numpy as np
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.run import run_virtual_circuit_dense
+
+    res = {"config": "syc_32_5_p2", "device": torch.cuda.get_device_name(0), "reps": 20}
+    _, cut, _ = cutting.config_cut_circuit("syc", 32, 5, 2)
+    virt = VirtualCircuit(cut)
+    red = KnitReducer(virt)
+    ctx = engine.get_context(0)
+    res["fragments"] = [{"rows": int(q.shape[0]), "m": len(cl)} for q, cl in zip(red.qs, red.clbits)]
+    res["terms"] = int(red.ops.num_terms)
+
+    def transposed_once():
+        red._transposed = None
+        return red.transposed_operands()
+
+    res["transposed_operands_once"] = timed(torch, transposed_once)
+    Xts = red.transposed_operands()
+    res["transposed_bytes"] = int(sum(x.numel() * 8 for x in Xts))
+    res["ldt"] = int(Xts[0].shape[1])
+    mats = engine.fragment_operands(ctx, red.ops, red.qs)
+    f = max(range(len(mats)), key=lambda i: mats[i].numel())
+    dst = torch.empty_like(Xts[f])
+    t = timed(torch, lambda: engine.transpose_rows(ctx, mats[f], len(red.clbits[f]), out=dst))
+    t.update(K=int(mats[f].shape[0]), m=len(red.clbits[f]), bytes_moved=int(mats[f].numel() * 8 + dst.numel() * 8))
+    t["GBs"] = t["bytes_moved"] / t["median_ms"] / 1e6
+    res["qk_transpose_rows"] = t
+
+    class OnOperands:  # KnitReducer._spectrum_chunks with X_f in the place of H_f: the gather route that exists today
+        device, clbits = red.device, red.clbits
+        z_spectrum = staticmethod(lambda: mats)
+
+    def torch_gather(zs):
+        return torch.cat([v for _, v in KnitReducer._spectrum_chunks(OnOperands, zs)])
+
+    rng = np.random.default_rng(0)
+    keys = rng.integers(0, 1 << 32, size=1 << 20, dtype=np.int64)
+    keys_d = torch.from_numpy(keys).cuda()
+    row_bytes = sum(8 * x.shape[1] for x in Xts)
+    for M in (1 << 10, 1 << 17, 1 << 20):
+        kd, out = keys_d[:M].contiguous(), torch.empty(M, dtype=torch.float64, device="cuda")
+        res[f"probabilities_{M}"] = timed(torch, lambda: red.probabilities(kd))
+        res[f"probabilities_host_keys_{M}"] = timed(torch, lambda: red.probabilities(keys[:M]))
+        t = timed(torch, lambda: engine.knit_at(ctx, Xts, red.clbits, kd, 0, out=out))
+        t["bytes_gathered"] = M * row_bytes
+        t["GBs"] = t["bytes_gathered"] / t["median_ms"] / 1e6
+        res[f"qk_knit_at_{M}"] = t
+        res[f"torch_gather_{M}"] = timed(torch, lambda: torch_gather(keys[:M]))
+        res[f"expectation_spectrum_{M}"] = timed(torch, lambda: red.expectation(keys[:M], method="spectrum"))
+        res[f"expectation_fused_{M}"] = timed(torch, lambda: red.expectation(keys[:M], method="fused"))
+    a, b = res[f"qk_knit_at_{1 << 20}"], res[f"torch_gather_{1 << 20}"]
+    res["verdict_2^20"] = {"kernel_median_ms": a["median_ms"], "torch_median_ms": b["median_ms"],
+                           "kernel_spread_ms": a["max_ms"] - a["min_ms"], "torch_spread_ms": b["max_ms"] - b["min_ms"],
+                           "kernel_faster_beyond_both_spreads": b["median_ms"] - a["median_ms"] > max(
+                               a["max_ms"] - a["min_ms"], b["max_ms"] - b["min_ms"])}
+    k10 = keys_d[:1 << 10]
+    res["check"] = {
+        "kernel_vs_torch_gather_max_abs_diff_2^17": float((red.probabilities(keys_d[:1 << 17])
+                                                           - torch_gather(keys[:1 << 17])).abs().max()),
+        "fused_vs_spectrum_max_abs_diff_2^17": float(abs(red.expectation(keys[:1 << 17], method="fused")
+                                                         - red.expectation(keys[:1 << 17], method="spectrum")).max())}
+    if not args.no_dense:
+        red._spectrum = red._spectrum_t = None  # the 2^32 output needs the room
+        torch.cuda.empty_cache()
+        full, _ = run_virtual_circuit_dense(virt)
+        res["check"]["kernel_vs_dense_max_abs_diff_2^10"] = float((red.probabilities(k10) - full[k10]).abs().max())
+        del full
+        res[f"dense_{1 << 10}"] = timed(torch, lambda: run_virtual_circuit_dense(virt)[0][k10])
+    print(json.dumps(res, indent=1), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--lookup", action="store_true", help="the probabilities-at-chosen-keys leg only (see lookup_leg)")
     ap.add_argument("--spectrum", action="store_true", help="the Walsh-Hadamard spectrum leg only (see spectrum_leg)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-dense", action="store_true", help="skip the dense route (needs 34 GB for the output)")
@@ -231,6 +321,8 @@ def main():
         return shots_leg(args)
     if args.spectrum:
         return spectrum_leg(args)
+    if args.lookup:
+        return lookup_leg(args)
     import torch
 
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
