@@ -148,6 +148,8 @@ SIGNATURES = {
     "qk_transpose_rows": (c_i32, [c_vp, c_i64, ctypes.c_int, c_vp, c_i64, c_vp, c_i64]),
     "qk_knit_at": (c_i32, [c_vp, ctypes.c_int, c_i64, c_i64, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int),
                            ctypes.POINTER(ctypes.c_int), c_vp, c_i64, c_u64, c_vp]),
+    "qk_gram_rows_workspace_bytes": (c_i32, [c_i64, c_i64, ctypes.c_int, ctypes.POINTER(c_i64)]),
+    "qk_gram_rows": (c_i32, [c_vp, c_i64, c_i64, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]),
 }
 
 _lock = threading.Lock()

@@ -820,6 +820,58 @@ def knit_at(ctx: Context, Xts: list, positions: list, keys, dead: int = 0, out=N
     return out
 
 
+def gram_rows(ctx: Context, A, B=None, m: int | None = None, out=None):
+    """``qk_gram_rows``: ``out[i, j] = sum over x < 2^m of A[i, x] * B[j, x]`` on the fp64 matrix cores ->
+    float64 ``[RA, RB]``. ``A``, ``B``: device float64 ``[>= 1, >= 2^m]`` with unit column stride, only read;
+    ``B=None`` is the symmetric case ``B = A`` (``out`` is then bitwise equal to its transpose). ``m`` defaults
+    to the column count of ``A``, which must then be a power of two. ``out`` (optional): a float64 ``[RA, RB]``
+    with unit column stride on the device of ``A`` that does not overlap the inputs. Deterministic: the split of
+    ``x`` depends on ``(RA, RB, m)`` alone (``observables.gram_split``)."""
+    T = torch()
+    if B is None:
+        B = A
+    for name, X in (("A", A), ("B", B)):
+        if X.dim() != 2 or X.dtype != T.float64 or X.shape[0] < 1 or (X.shape[1] > 1 and X.stride(1) != 1) or not X.is_cuda:
+            raise ValueError(f"{name} must be a device float64 [rows >= 1, >= 2^m] with unit column stride")
+    if B.device != A.device:
+        raise ValueError("A and B must be on one device")
+    if m is None:
+        cols = A.shape[1]
+        if cols < 1 or cols & (cols - 1):
+            raise ValueError(f"A has {cols} columns, not a power of two: pass m")
+        m = cols.bit_length() - 1
+    m = int(m)
+    if not 0 <= m <= 30:
+        raise ValueError(f"m must be in 0..30, not {m}")
+    n = 1 << m
+    if A.shape[1] < n or B.shape[1] < n:
+        raise ValueError(f"A has {A.shape[1]} and B {B.shape[1]} columns for m = {m}")
+    RA, RB = A.shape[0], B.shape[0]
+    lda = A.stride(0) if RA > 1 else max(A.stride(0), n)
+    ldb = B.stride(0) if RB > 1 else max(B.stride(0), n)
+    if lda < n or ldb < n:
+        raise ValueError(f"row stride below 2^m = {n}")
+    if out is None:
+        out = T.empty((RA, RB), dtype=T.float64, device=A.device)
+    if out.dim() != 2 or out.dtype != T.float64 or tuple(out.shape) != (RA, RB) or (RB > 1 and out.stride(1) != 1) or (
+            out.device != A.device):
+        raise ValueError(f"out must be float64 [{RA}, {RB}] with unit column stride on the device of A")
+    ldg = out.stride(0) if RA > 1 else max(out.stride(0), RB)
+    if ldg < RB:
+        raise ValueError(f"row stride of out below {RB}")
+    g0 = out.data_ptr()
+    g1 = g0 + ((RA - 1) * ldg + RB) * 8
+    for X, rows, ld in ((A, RA, lda), (B, RB, ldb)):
+        if X.data_ptr() < g1 and g0 < X.data_ptr() + ((rows - 1) * ld + n) * 8:
+            raise ValueError("out overlaps A or B")
+    need = ctypes.c_int64()
+    ctx.check(ctx.lib.qk_gram_rows_workspace_bytes(RA, RB, m, ctypes.byref(need)), "qk_gram_rows_workspace_bytes")
+    work = T.empty(need.value // 8, dtype=T.float64, device=A.device) if need.value else None
+    ctx.check(ctx.lib.qk_gram_rows(ctx.handle, RA, RB, m, A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldg,
+                                   _ptr(work), need.value), "qk_gram_rows")
+    return out
+
+
 # ----------------------------------------------------------------------------- shot sampling
 _SEED_STRIDE = 0x632BE59BD9B4E019  # per-fragment stream offset (mirrored by oracle/sampling.py)
 _U64 = (1 << 64) - 1

@@ -24,6 +24,11 @@ csrc/qknit_lookup.hip) the factors a key takes from a fragment are one contiguou
 sums their products over the terms: :meth:`KnitReducer.probabilities`, ``linear_xeb``,
 ``fidelity_to_counts``, and ``expectation(method="fused")`` on the transposed spectrum.
 
+Second moments factorise too: ``sum_x R[x] R'[x] = sum_{k,k'} prod_f (X_f X'_f^T)[k][k']``, and
+``X_f X'_f^T = W_f^T (q_f q'_f^T) W'_f`` needs one tall product per fragment, the cross-Gram of the swept rows
+(``qk_gram_rows``, csrc/qknit_moments.hip): :meth:`KnitReducer.overlap`, ``collision_probability``,
+``renyi2_entropy``, ``ideal_xeb``, ``l2_distance``, ``mutual_information2``.
+
 It builds on the direct path (``engine.prepare_fragments`` / ``sweep_fragment`` / ``knit_operands``
 / ``fragment_operands`` / ``contract``, as ``run._direct_dense``), not on the cached
 ``KnitPipeline``: the pipeline's row pruning rests on a per-entry bound on ``R`` and a marginal sums
@@ -313,6 +318,137 @@ def knit_at_host(Xs: list, positions: list, keys, dead: int = 0) -> np.ndarray:
     return out
 
 
+def gram_host(A, B=None, m: int | None = None) -> np.ndarray:
+    """numpy model of ``qk_gram_rows`` in ``np.longdouble``: ``G[i, j] = sum_{x < 2^m} A[i, x] * B[j, x]``
+    (``B=None``: ``B = A``; ``m=None``: every column of ``A``)."""
+    A = np.asarray(A, dtype=np.longdouble)
+    B = A if B is None else np.asarray(B, dtype=np.longdouble)
+    n = A.shape[1] if m is None else 1 << int(m)
+    if A.shape[1] < n or B.shape[1] < n:
+        raise ValueError(f"{A.shape[1]} and {B.shape[1]} columns for {n} outcomes")
+    return A[:, :n] @ B[:, :n].T
+
+
+def gram_split(RA: int, RB: int, m: int, block: int = 64, min_groups: int = 512, max_split: int = 256,
+               min_chunk: int = 256) -> dict:
+    """The decomposition ``qk_gram_rows`` uses for a shape (qknit_moments.hip: gr_make_shape): ``ba x bb``
+    blocks of ``block x block`` row pairs, the ``2^m`` outcomes cut into ``split`` equal chunks
+    ``chunks[s] = (x0, x1)``, ascending; a function of ``(RA, RB, m)`` alone."""
+    if RA < 1 or RB < 1 or not 0 <= m <= 30:
+        raise ValueError(f"RA, RB >= 1 and 0 <= m <= 30, not ({RA}, {RB}, {m})")
+    ba, bb, W = -(-RA // block), -(-RB // block), 1 << m
+    split = 1
+    while ba * bb * split < min_groups and split < max_split and W // (2 * split) >= min_chunk:
+        split *= 2
+    chunk = W // split
+    return dict(ba=ba, bb=bb, split=split, chunk=chunk, chunks=[(s * chunk, (s + 1) * chunk) for s in range(split)],
+                workspace_bytes=0 if split == 1 else ba * bb * split * block * block * 8)
+
+
+def second_moment_host(Xs: list, Ys: list | None = None) -> np.longdouble:
+    """``sum_x R[x] R'[x]`` of two knits ``R = sum_k prod_f Xs[f][k, x_f]``, ``R' = sum_k' prod_f Ys[f][k', x_f]``
+    over the same fragments, in ``np.longdouble``: ``sum_{k, k'} prod_f (X_f Y_f^T)[k, k']``. ``Ys=None``:
+    ``R' = R``."""
+    Ys = Xs if Ys is None else Ys
+    if len(Xs) != len(Ys) or not Xs:
+        raise ValueError(f"{len(Xs)} and {len(Ys)} fragments")
+    prod = None
+    for X, Y in zip(Xs, Ys):
+        G = gram_host(X, Y)
+        prod = G if prod is None else prod * G
+    return prod.sum()
+
+
+def match_fragments(clbits_a: list, clbits_b: list, kept) -> tuple:
+    """Pair the fragments of two partitions of the clbits, restricted to ``kept``. ``clbits_a[f]`` /
+    ``clbits_b[g]``: the clbits of a fragment's outcome bits in local bit order. Two fragments are paired when
+    they hold the same set of kept clbits, wherever they stand in their lists. Returns
+    ``(pairs, only_a, only_b)``: ``pairs`` a list of ``(f, g, order)`` with ``order`` ``None`` where the kept
+    clbits come in the same local order on both sides, else the list whose entry ``i`` is the bit of g's
+    reduced index that holds bit ``i`` of f's; ``only_a`` / ``only_b`` the fragments with no kept clbit, which
+    need no partner. ``ValueError``, naming the clbits, when the two partitions of ``kept`` differ."""
+    kept = {int(c) for c in kept}
+    seq_a = [[int(c) for c in fcl if int(c) in kept] for fcl in clbits_a]
+    seq_b = [[int(c) for c in fcl if int(c) in kept] for fcl in clbits_b]
+    by_set = {frozenset(s): g for g, s in enumerate(seq_b) if s}
+    pairs, used = [], set()
+    for f, s in enumerate(seq_a):
+        if not s:
+            continue
+        g = by_set.get(frozenset(s))
+        if g is None or g in used:
+            theirs = sorted(sorted(t) for t in seq_b if set(t) & set(s))
+            raise ValueError(f"the fragments cut the clbits differently: {sorted(s)} on one side, {theirs} on the other")
+        used.add(g)
+        pairs.append((f, g, None if seq_b[g] == s else [seq_b[g].index(c) for c in s]))
+    for g, s in enumerate(seq_b):
+        if s and g not in used:
+            raise ValueError(f"the fragments cut the clbits differently: {sorted(s)} on one side only")
+    return pairs, [f for f, s in enumerate(seq_a) if not s], [g for g, s in enumerate(seq_b) if not s]
+
+
+MOMENT_WORK_BYTES = 256 << 20  # the [rows, K'] temporaries of KnitReducer.overlap: K beyond it goes in row blocks
+
+
+def _ones_spec(T, dev, K: int) -> tuple:
+    """The gather that repeats row 0 ``K`` times with coefficient 1: the operand of an ``m = 0`` factor of ones."""
+    return ("G", T.zeros(K, dtype=T.int64, device=dev), T.ones(K, dtype=T.float64, device=dev))
+
+
+def _permute_bits(T, rows, order):
+    """``rows`` re-indexed so that bit ``i`` of the new column index is bit ``order[i]`` of the old one."""
+    if order is None:
+        return rows
+    y = T.arange(rows.shape[1], dtype=T.int64, device=rows.device)
+    return rows.index_select(1, deposit_bits(T.zeros_like(y), y, order))
+
+
+def overlap_of_sides(ctx, side_a: tuple, side_b, kept) -> float:
+    """``sum_{k, k'} prod_f G_f[k, k']`` of two sides ``(rows, specs, clbits, K)``, the work of
+    :meth:`KnitReducer.overlap`. ``rows[f]``: device float64 ``[R_f, 2^k_f]``, a fragment's rows reduced onto its
+    kept clbits (column bit ``i`` = its ``i``-th kept clbit in ``clbits[f]`` order); ``specs[f]``: how its operand
+    ``X_f [K, 2^k_f]`` follows from them, ``("T", W^T [R_f, K])`` for ``X_f = W rows`` or ``("G", idx [K], coefs [K])``
+    for ``X_f[k] = coefs[k] rows[idx[k]]``, on the device; ``clbits[f]``: the fragment's clbits in local bit order;
+    ``K``: the number of terms. ``side_b=None``: the side itself (the Grams are then symmetric calls). The
+    fragments are paired by :func:`match_fragments` on ``kept``; where the local bit orders of a pair differ the
+    columns of b's rows are permuted to a's order."""
+    T = engine.torch()
+    same = side_b is None
+    qa, sa, cla, Ka = side_a
+    qb, sb, clb, Kb = side_a if same else side_b
+    dev = qa[0].device
+    pairs, only_a, only_b = match_fragments(cla, clb, kept)
+    one = T.ones((1, 1), dtype=T.float64, device=dev)
+    # (rows_a, spec_a, rows_b, spec_b, symmetric): an unpaired fragment meets a row of one 1.0 gathered K times
+    work = [(qa[f], sa[f], _permute_bits(T, qb[g], order), sb[g], same and f == g) for f, g, order in pairs]
+    work += [(qa[f], sa[f], one, _ones_spec(T, dev, Kb), False) for f in only_a]
+    work += [(one, _ones_spec(T, dev, Ka), qb[g], sb[g], False) for g in only_b]
+    halves = []  # per fragment: Gq applied to the b side, [R_a, K']
+    for ra, _, rb, spec_b, sym in work:
+        m = ra.shape[1].bit_length() - 1
+        if spec_b[0] == "T":  # H = Gq W' = (Gq^T)^T W': the Gram is formed transposed
+            GqT = engine.gram_rows(ctx, ra, None, m) if sym else engine.gram_rows(ctx, rb, ra, m)
+            H = T.empty((ra.shape[0], Kb), dtype=T.float64, device=dev)
+            halves.append(engine.gemm_keyed(ctx, GqT, spec_b[1], out=H, strideA=Kb))
+        else:
+            Gq = engine.gram_rows(ctx, ra, None if sym else rb, m)
+            halves.append(Gq.index_select(1, spec_b[1]) * spec_b[2])
+    step = max(1, MOMENT_WORK_BYTES // (16 * Kb))
+    sums = T.empty(Ka, dtype=T.float64, device=dev)
+    for k0 in range(0, Ka, step):
+        k1 = min(k0 + step, Ka)
+        prod = None
+        for (_, spec_a, _, _, _), H in zip(work, halves):
+            if spec_a[0] == "T":  # G_f[k0:k1] = (W^T[:, k0:k1])^T H
+                G = T.empty((k1 - k0, Kb), dtype=T.float64, device=dev)
+                engine.gemm_keyed(ctx, spec_a[1][:, k0:k1], H, out=G, strideA=Kb)
+            else:
+                G = H.index_select(0, spec_a[1][k0:k1]) * spec_a[2][k0:k1, None]
+            prod = G if prod is None else prod.mul_(G)
+        T.sum(prod, dim=1, out=sums[k0:k1])  # a row's K' products, then the rows: two fixed trees
+    return float(sums.sum())
+
+
 def _user_order(T, asc_result, clbits: list):
     """Result indexed with bit i = clbits[i], from the one indexed by the ascending clbits."""
     order = sorted(clbits)
@@ -348,6 +484,7 @@ class KnitReducer:
         self.clbits = [list(c) for c in self.ops.clbits]
         self._spectrum = None  # z_spectrum(): formed on first use
         self._transposed = None  # transposed_operands(): formed on first use
+        self._moment_specs = None  # _moment_sides(): the transforms / gathers on the device, formed on first use
         self._spectrum_t = None  # the spectrum transposed (expectation(method="fused")): formed on first use
         if not self.frags:  # no fragment at all: the knit is the sum of the coefficients at key 0
             vg = [v.operation for v in virt.vgate_instructions]
@@ -616,6 +753,86 @@ class KnitReducer:
                                 for H, fcl in zip(self.z_spectrum(), self.clbits)]
         # a Z on a clbit nobody measures is +1: its bit is not read, and no key is dead
         return engine.knit_at(self.ctx, self._spectrum_t, self.clbits, self._device_keys(ks), 0).cpu().numpy()
+
+    # -- second moments: overlaps of knits --------------------------------------------------------
+    def _moment_sides(self, cl: list) -> tuple:
+        """``(rows, specs, clbits, K)`` for :func:`overlap_of_sides`: per fragment its swept rows reduced onto the
+        kept clbits ``[R_f, 2^k_f]``, how its operand follows from them (``("T", W^T [R_f, K])`` or
+        ``("G", rows [K], coefs [K])``, on the device: uploaded on first use and kept), and its clbits. No
+        fragment at all is one ``m = 0`` fragment whose single row holds ``_scalar``."""
+        T = engine.torch()
+        dev = T.device("cuda", self.device)
+        if not self.frags:
+            one = T.full((1, 1), self._scalar, dtype=T.float64, device=dev)
+            return [one], [_ones_spec(T, dev, 1)], [[]], 1
+        if self._moment_specs is None:
+            specs = []
+            for W, rows, coefs in zip(self.ops.transforms, self.ops.rows, self.ops.coefs):
+                if W is not None:
+                    specs.append(("T", T.from_numpy(np.ascontiguousarray(W.T)).to(dev)))
+                else:
+                    specs.append(("G", T.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(dev),
+                                  T.from_numpy(np.ascontiguousarray(coefs, dtype=np.float64)).to(dev)))
+            self._moment_specs = specs
+        keep, _ = split_clbits(cl, self.clbits)
+        rows = [q if kp == (1 << len(fcl)) - 1 else engine.reduce_bits(self.ctx, q, len(fcl), kp, [0])
+                for q, fcl, kp in zip(self.qs, self.clbits, keep)]
+        return rows, self._moment_specs, self.clbits, self.ops.num_terms
+
+    def overlap(self, other=None, clbits=None) -> float:
+        """``sum_y R_S[y] R'_S[y]``: the overlap of this knit's marginal onto ``clbits`` (``None``: all clbits)
+        with that of ``other`` (another reducer on the same device with as many clbits; ``None``: itself),
+        without either output (DESIGN.md §4a "Second moments"). The clbit supports of the fragments are
+        disjoint, so the sum is ``sum_{k, k'} prod_f G_f[k, k']`` with ``G_f = X_f X'_f^T``: per fragment the
+        swept rows are reduced onto the kept clbits (``qk_reduce_bits``), their cross-Gram is one
+        ``qk_gram_rows`` and ``G_f`` follows through the two transforms (or row gathers); the product over
+        the fragments and the sum over ``(k, k')`` run in row blocks of at most ``MOMENT_WORK_BYTES``.
+        Restricted to ``clbits`` the fragments of the two reducers must measure the same sets of clbits, in
+        any order (:func:`match_fragments`; ``ValueError`` otherwise); a fragment with no kept clbit enters
+        with its row sums. Every sum has a fixed order: two calls return the same float."""
+        self.ctx.bind_stream()
+        same = other is None or other is self
+        if not same:
+            if not isinstance(other, KnitReducer):
+                raise ValueError("other must be a KnitReducer or None")
+            if other.N != self.N:
+                raise ValueError(f"{self.N} clbits against {other.N}")
+            if other.device != self.device:
+                raise ValueError(f"reducers on devices {self.device} and {other.device}")
+        cl = list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+        return overlap_of_sides(self.ctx, self._moment_sides(cl), None if same else other._moment_sides(cl), cl)
+
+    def collision_probability(self, clbits=None) -> float:
+        """``sum_y R_S[y]^2`` of the marginal onto ``clbits`` (``None``: all): :meth:`overlap` with itself."""
+        return self.overlap(None, clbits)
+
+    def renyi2_entropy(self, clbits=None) -> float:
+        """The Rényi-2 entropy ``-log2(sum_y p[y]^2)`` in bits of ``p = R_S / mass``, the marginal onto
+        ``clbits`` normalised by the knit's signed total ``mass = expectation([0])[0]`` (as
+        :meth:`fidelity_to_counts` normalises)."""
+        mass = float(self.expectation([0])[0])
+        return float(-np.log2(self.collision_probability(clbits) / mass ** 2))
+
+    def ideal_xeb(self, clbits=None) -> float:
+        """The linear XEB score an ideal sampler of this knit would reach in expectation:
+        ``D * sum_y R_S[y]^2 - 1`` with ``D`` as in :meth:`linear_xeb`; about 1 for a Porter-Thomas output."""
+        cl = range(self.N) if clbits is None else clbits
+        measured = {c for fcl in self.clbits for c in fcl}
+        return self.collision_probability(clbits) * 2.0 ** sum(1 for c in cl if int(c) in measured) - 1.0
+
+    def l2_distance(self, other, clbits=None) -> float:
+        """``||R_S - R'_S||_2 = sqrt(max(s_aa - 2 s_ab + s_bb, 0))`` from three overlaps. The three sums cancel:
+        a distance below about ``sqrt(2^-52 * (s_aa + s_bb))`` is rounding, whatever it reads."""
+        s_ab = self.overlap(other, clbits)  # first: it checks other and the pairing
+        s_aa, s_bb = self.overlap(None, clbits), other.overlap(None, clbits)
+        return float(np.sqrt(max(s_aa - 2.0 * s_ab + s_bb, 0.0)))
+
+    def mutual_information2(self, a, b) -> float:
+        """``S2(a) + S2(b) - S2(a + b)`` in bits for two disjoint lists of clbits (:meth:`renyi2_entropy`)."""
+        a, b = check_clbits(a, self.N), check_clbits(b, self.N)
+        if set(a) & set(b):
+            raise ValueError(f"clbits {sorted(set(a) & set(b))} in both lists")
+        return self.renyi2_entropy(a) + self.renyi2_entropy(b) - self.renyi2_entropy(a + b)
 
     def marginal_parity(self, clbits, masks):
         """The mixed form: device fp64 ``[M, 2^k]``, row j the marginal onto ``clbits`` of

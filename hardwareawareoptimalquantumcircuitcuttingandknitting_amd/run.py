@@ -612,3 +612,30 @@ def run_virtual_circuit_xeb(virt: VirtualCircuit, keys, *, clbits=None, device: 
     now = perf_counter()
     score = red.linear_xeb(keys, clbits)
     return score, RunTimeInfo(run_time, perf_counter() - now)
+
+
+def run_virtual_circuit_collision(virt: VirtualCircuit, clbits=None, *, device: int = 0, factored: bool | None = None,
+                                  group=None, sample: bool = False):
+    """The collision probability ``sum_y R_S[y]^2`` of the exact knit's marginal onto ``clbits`` (``None`` =
+    all clbits), without the 2^N output: per fragment the Gram matrix of its swept rows (``qk_gram_rows``),
+    then sums over pairs of terms (:meth:`observables.KnitReducer.collision_probability`). Returns
+    ``(float, RunTimeInfo)``; the sweep is ``run_time``, Grams + combine ``knit_time``. Same restrictions as
+    :func:`run_virtual_circuit_marginal`."""
+    red, run_time = _reducer(virt, device, factored, group, sample)
+    now = perf_counter()
+    value = red.collision_probability(clbits)
+    return value, RunTimeInfo(run_time, perf_counter() - now)
+
+
+def run_virtual_circuit_overlap(virt_a: VirtualCircuit, virt_b: VirtualCircuit, clbits=None, *, device: int = 0,
+                                factored: bool | None = None, group=None, sample: bool = False):
+    """The overlap ``sum_y R_S[y] R'_S[y]`` of the exact knits of two cut circuits, marginalised onto
+    ``clbits`` (``None`` = all), without either 2^N output (:meth:`observables.KnitReducer.overlap`). The two
+    circuits must have the same number of clbits and, on ``clbits``, fragments that measure the same sets.
+    Returns ``(float, RunTimeInfo)``; both sweeps are ``run_time``. Same restrictions as
+    :func:`run_virtual_circuit_marginal`."""
+    red_a, time_a = _reducer(virt_a, device, factored, group, sample)
+    red_b, time_b = _reducer(virt_b, device, factored, group, sample)
+    now = perf_counter()
+    value = red_a.overlap(red_b, clbits)
+    return value, RunTimeInfo(time_a + time_b, perf_counter() - now)

@@ -555,6 +555,21 @@ int qk_transpose_rows(qk_ctx* ctx, int64_t K, int m, const double* X, int64_t ld
 int qk_knit_at(qk_ctx* ctx, int F, int64_t K, int64_t ldt, const double* const* Xt, const int* m, const int* pos,
                const int64_t* keys, int64_t n, uint64_t dead, double* out);
 
+/* ---- second moments of the knit (qknit_moments.hip): the cross-Gram of two tall row sets -----------------
+ * qk_gram_rows: G[i * ldg + j] = sum_{x < 2^m} A[i * lda + x] * B[j * ldb + x] for i < RA, j < RB, on the fp64
+ * matrix cores. RA, RB >= 1, 0 <= m <= 30, lda, ldb >= 2^m (rows at any 8-byte offset), ldg >= RB. A, B, G
+ * and ws are DEVICE buffers; A and B are only read and may be the same buffer (A == B with lda == ldb is the
+ * symmetric case); G must not overlap them. `ws`: qk_gram_rows_workspace_bytes(RA, RB, m) bytes (0 where the
+ * reduction is not split; ws may then be null).
+ * Deterministic: no atomics. x is cut into S chunks, S a function of (RA, RB, m) alone; a chunk's partial is
+ * one accumulator chain over its x ascending, 4 per step, and the partials are added in ascending chunk
+ * order. Two launches give identical bits, a row pair's value does not depend on the other rows of the same
+ * (RA, RB, m), and for A == B G[i][j] and G[j][i] are bit-identical.
+ * |G - exact| <= 2^m * 2^-53 * sum_x |A[i][x]| |B[j][x]|. */
+int qk_gram_rows_workspace_bytes(int64_t RA, int64_t RB, int m, int64_t* bytes);
+int qk_gram_rows(qk_ctx* ctx, int64_t RA, int64_t RB, int m, const double* A, int64_t lda, const double* B,
+                 int64_t ldb, double* G, int64_t ldg, void* ws, int64_t ws_bytes);
+
 int qk_hellinger(qk_ctx* ctx, int64_t n, const double* p, const double* q, double* acc3);
 
 #ifdef __cplusplus

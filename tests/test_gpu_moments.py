@@ -1,0 +1,520 @@
+"""Second moments of the knit, on the GPU: ``qk_gram_rows`` against the longdouble model, and
+``KnitReducer.overlap`` / ``collision_probability`` / ``renyi2_entropy`` / ``ideal_xeb`` / ``l2_distance`` /
+``mutual_information2`` and the ``run_virtual_circuit_collision`` / ``run_virtual_circuit_overlap`` entry points
+against the oracle's dense knit."""
+import ctypes
+import functools
+import math
+
+import numpy as np
+import pytest
+
+import obs_cases
+from oracle import dense, qvm, tables
+from test_gpu_lookup import CASES, DIRECT_ONLY, _case
+from test_observables import np_marginal
+
+from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import (RunTimeInfo, VirtualCircuit, cutting, engine,
+                                                                      run_virtual_circuit_collision,
+                                                                      run_virtual_circuit_overlap)
+from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import (KnitReducer, gram_host, gram_split,
+                                                                                  match_fragments, overlap_of_sides,
+                                                                                  second_moment_host)
+
+pytestmark = pytest.mark.gpu
+EPS = 2.0 ** -53
+TOL = 1e-12  # the project's parity tolerance
+ROWS = (1, 3, 16, 17, 65)
+PAD = 1e300
+
+
+@pytest.fixture(scope="module")
+def T(require_gpu):
+    import torch
+
+    return torch
+
+
+def _padded(T, rng, rows, W, pad):
+    """Device rows [rows, W] inside a wider buffer whose other columns hold 1e300; the host copy of the rows."""
+    host = np.full((rows, W + pad), PAD)
+    host[:, :W] = rng.standard_normal((rows, W))
+    buf = T.from_numpy(host).cuda()
+    return buf, buf[:, :W], host[:, :W]
+
+
+def _reference(A, B, m):
+    """(exact, band): the longdouble Gram and 2^m 2^-53 (|A| |B|^T), the bound of a dot product of 2^m terms in
+    any order (the scale itself in float64: its own rounding is 2^m 2^-53 of the band)."""
+    W = 1 << m
+    return gram_host(A, B, m), (1 << m) * EPS * (np.abs(A[:, :W]) @ np.abs(B[:, :W]).T)
+
+
+def _worst(got, exact, band, what):
+    """The worst fraction of the band; fails outside it."""
+    err = np.abs(got.astype(np.longdouble) - exact)
+    frac = float((err / band).max())
+    assert np.all(err <= band), (what, frac)
+    return frac
+
+
+# ----------------------------------------------------------------------------- 1. the kernel vs longdouble
+@pytest.mark.parametrize("m", [0, 1, 5, 10, 13])
+def test_gram_rows_matches_the_longdouble_model_within_the_derived_band(T, m):
+    """Every (RA, RB) takes the leading rows of one pair of 65-row sets, so one reference serves them all."""
+    ctx = engine.get_context(0)
+    W = 1 << m
+    rng = np.random.default_rng(m)
+    bufA, A65, Ah = _padded(T, rng, ROWS[-1], W, 3)
+    bufB, B65, Bh = _padded(T, rng, ROWS[-1], W, 5)
+    keepA, keepB = bufA.clone(), bufB.clone()
+    exact, band = _reference(Ah, Bh, m)
+    worst = 0.0
+    for RA in ROWS:
+        for RB in ROWS:
+            A, B = A65[:RA], B65[:RB]
+            G = engine.gram_rows(ctx, A, B, m)
+            assert tuple(G.shape) == (RA, RB) and G.dtype == T.float64 and G.is_cuda
+            got = G.cpu().numpy()
+            assert np.isfinite(got).all() and np.abs(got).max() < 1e100, "the padding was read"
+            worst = max(worst, _worst(got, exact[:RA, :RB], band[:RA, :RB], (RA, RB)))
+    assert T.equal(bufA, keepA) and T.equal(bufB, keepB), "an input was written"
+    print(f"m = {m}: worst error {worst:.3g} of the band")
+    # out= is honoured, inside a wider prefilled buffer whose other columns stay; m defaults to the column count
+    RA, RB = 17, 65
+    A, B, Ah17 = A65[:RA], B65[:RB], Ah[:RA]
+    G = engine.gram_rows(ctx, A, B, m)
+    wide = T.full((RA, RB + 2), 7.0, dtype=T.float64, device="cuda")
+    assert engine.gram_rows(ctx, A, B, m, out=wide[:, :RB]).data_ptr() == wide.data_ptr()
+    assert T.equal(wide[:, :RB], G) and bool((wide[:, RB:] == 7.0).all())
+    assert T.equal(engine.gram_rows(ctx, A.contiguous(), B.contiguous()), G)
+    # the symmetric case, and a workspace of exactly the size the query names
+    S = engine.gram_rows(ctx, A)
+    _worst(S.cpu().numpy(), *_reference(Ah17, Ah17, m), "symmetric")
+    need = ctypes.c_int64(-1)
+    assert ctx.lib.qk_gram_rows_workspace_bytes(RA, RB, m, ctypes.byref(need)) == 0
+    assert need.value == gram_split(RA, RB, m)["workspace_bytes"]
+    ws = T.empty(max(need.value // 8, 1), dtype=T.float64, device="cuda")
+    out = T.full((RA, RB), 7.0, dtype=T.float64, device="cuda")
+    assert ctx.lib.qk_gram_rows(ctx.handle, RA, RB, m, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0),
+                                out.data_ptr(), RB, ws.data_ptr(), need.value) == 0
+    assert T.equal(out, G)
+
+
+def test_gram_rows_multi_chunk_tall_rows(T):
+    """[64, 2^16] x [64, 2^16]: a single block of row pairs, the outcomes in 256 chunks."""
+    ctx = engine.get_context(0)
+    m, R = 16, 64
+    sh = gram_split(R, R, m)
+    assert sh["split"] == 256 and sh["ba"] == sh["bb"] == 1
+    rng = np.random.default_rng(16)
+    bufA, A, Ah = _padded(T, rng, R, 1 << m, 1)
+    bufB, B, Bh = _padded(T, rng, R, 1 << m, 7)
+    G = engine.gram_rows(ctx, A, B, m)
+    frac = _worst(G.cpu().numpy(), *_reference(Ah, Bh, m), "cross")
+    S = engine.gram_rows(ctx, A)
+    frac_s = _worst(S.cpu().numpy(), *_reference(Ah, Ah, m), "symmetric")
+    print(f"[64, 2^16]: worst error {frac:.3g} (cross), {frac_s:.3g} (symmetric) of the band")
+    assert T.equal(S, S.T) and T.equal(engine.gram_rows(ctx, A, B, m), G)
+
+
+@pytest.mark.parametrize("m", [1, 5, 10])
+def test_gram_rows_of_one_buffer_with_different_row_counts(T, m):
+    """A and B the same pointer and stride but RA != RB, in both directions, within a block and across the
+    64-row block boundary (a diagonal block then holds more rows of one side than of the other)."""
+    ctx = engine.get_context(0)
+    rng = np.random.default_rng(50 + m)
+    buf, X, Xh = _padded(T, rng, 130, 1 << m, 3)
+    exact, band = _reference(Xh, Xh, m)
+    for RA, RB in ((3, 130), (130, 3), (3, 17), (17, 3), (65, 130), (130, 65), (64, 65), (1, 64)):
+        A, B = X[:RA], X[:RB]
+        assert A.data_ptr() == B.data_ptr() and A.stride(0) == B.stride(0)
+        G = engine.gram_rows(ctx, A, B, m)
+        _worst(G.cpu().numpy(), exact[:RA, :RB], band[:RA, :RB], (RA, RB))
+        assert T.equal(G, engine.gram_rows(ctx, A, B.clone(), m)), (RA, RB)  # the bits of the general path
+        assert T.equal(G, engine.gram_rows(ctx, B, A, m).T), (RA, RB)
+
+
+# ----------------------------------------------------------------------------- 2. exactness
+@pytest.mark.parametrize("m", [0, 1, 5, 10, 13])
+def test_gram_rows_is_exact_on_small_integers(T, m):
+    ctx = engine.get_context(0)
+    W = 1 << m
+    for RA, RB in ((1, 1), (3, 17), (16, 16), (17, 65), (65, 65), (65, 3)):
+        rng = np.random.default_rng(7 * m + RA + 3 * RB)
+        A = rng.integers(-3, 4, size=(RA, W))
+        B = rng.integers(-3, 4, size=(RB, W))
+        got = engine.gram_rows(ctx, T.from_numpy(A.astype(np.float64)).cuda(), T.from_numpy(B.astype(np.float64)).cuda(), m)
+        assert np.array_equal(got.cpu().numpy(), (A @ B.T).astype(np.float64)), (RA, RB)
+        sym = engine.gram_rows(ctx, T.from_numpy(A.astype(np.float64)).cuda())
+        assert np.array_equal(sym.cpu().numpy(), (A @ A.T).astype(np.float64)), RA
+
+
+# ----------------------------------------------------------------------------- 3. fixed association
+@pytest.mark.parametrize("R,m", [(65, 13), (17, 10), (130, 5), (64, 16), (3, 1)])
+def test_gram_rows_bits_are_fixed_by_the_shape(T, R, m):
+    ctx = engine.get_context(0)
+    rng = np.random.default_rng(R + m)
+    W = 1 << m
+    A = T.from_numpy(rng.standard_normal((R, W))).cuda()
+    B = T.from_numpy(rng.standard_normal((R, W))).cuda()
+    G = engine.gram_rows(ctx, A, B, m)
+    assert T.equal(engine.gram_rows(ctx, A, B, m), G), "two launches differ"
+    S = engine.gram_rows(ctx, A)
+    assert T.equal(S, S.T), "A == B must give a bitwise symmetric G"
+    assert T.equal(engine.gram_rows(ctx, A, A, m), S)
+    # a copy of A as B takes the general path and gives the same bits
+    assert T.equal(engine.gram_rows(ctx, A, A.clone(), m), S)
+    # other contents in the other rows: the pair (i, j) keeps its bits
+    for i, j in ((0, 0), (R - 1, R // 2), (R // 3, R - 1)):
+        A2 = T.from_numpy(rng.standard_normal((R, W))).cuda()
+        B2 = T.from_numpy(rng.standard_normal((R, W))).cuda()
+        A2[i], B2[j] = A[i], B[j]
+        G2 = engine.gram_rows(ctx, A2, B2, m)
+        assert G2[i, j].item() == G[i, j].item() and not T.equal(G2, G), (i, j)
+
+
+# ----------------------------------------------------------------------------- 4. bad arguments
+def test_gram_rows_rejects_bad_arguments(T):
+    ctx = engine.get_context(0)
+    lib = ctx.lib
+    A = T.ones((4, 8), dtype=T.float64, device="cuda")
+    B = T.ones((3, 8), dtype=T.float64, device="cuda")
+    big = T.ones((64, 1 << 16), dtype=T.float64, device="cuda")  # split: needs a workspace
+    G = T.full((64, 64), -7.0, dtype=T.float64, device="cuda")
+
+    def gram(RA=4, RB=3, m=3, A_p=A.data_ptr(), lda=8, B_p=B.data_ptr(), ldb=8, G_p=G.data_ptr(), ldg=64, ws=None, ws_bytes=0):
+        return lib.qk_gram_rows(ctx.handle, RA, RB, m, A_p, lda, B_p, ldb, G_p, ldg, ws, ws_bytes)
+
+    bad = {"m must be": dict(m=31), "m must be in": dict(m=-1), "RA and RB": dict(RA=0), "at least 1": dict(RB=0),
+           "lda or ldb": dict(lda=7), "ldb < 2^m": dict(ldb=7), "ldg": dict(ldg=2), "null buffer": dict(A_p=None),
+           "overlaps": dict(G_p=A.data_ptr() + 8, ldg=3), "G overlaps": dict(G_p=B.data_ptr() - 8 * 10, ldg=3)}
+    for msg, kw in bad.items():
+        assert gram(**kw) != 0, kw
+        assert msg.encode() in lib.qk_last_error(ctx.handle), (kw, lib.qk_last_error(ctx.handle))
+    for kw in (dict(B_p=None), dict(G_p=None)):
+        assert gram(**kw) != 0 and b"null buffer" in lib.qk_last_error(ctx.handle), kw
+    need = ctypes.c_int64()
+    assert lib.qk_gram_rows_workspace_bytes(64, 64, 16, ctypes.byref(need)) == 0 and need.value > 0
+    ws = T.empty(need.value // 8, dtype=T.float64, device="cuda")
+    tall = dict(RA=64, RB=64, m=16, A_p=big.data_ptr(), lda=1 << 16, B_p=big.data_ptr(), ldb=1 << 16)
+    for kw in (dict(ws=None, ws_bytes=0), dict(ws=ws.data_ptr(), ws_bytes=need.value - 8), dict(ws=None, ws_bytes=need.value)):
+        assert gram(**tall, **kw) != 0 and b"workspace too small" in lib.qk_last_error(ctx.handle), kw
+    T.cuda.synchronize()
+    assert bool((G == -7.0).all()) and bool((A == 1.0).all())  # nothing ran
+    assert gram(**tall, ws=ws.data_ptr(), ws_bytes=need.value) == 0
+    assert gram(G_p=G.data_ptr() + 8 * 64 * 32) == 0  # rows 32..35, columns 0..2 of G
+    T.cuda.synchronize()
+    assert bool((G[:32] == 65536.0).all()) and bool((G[32:36, :3] == 8.0).all()) and bool((G[36:] == 65536.0).all())
+
+    # the engine wrapper raises before any launch
+    out = T.full((4, 3), -7.0, dtype=T.float64, device="cuda")
+    for kw in (dict(m=31), dict(m=4), dict(A=A.float()), dict(B=B.float()), dict(A=A.cpu()), dict(B=B.cpu()), dict(A=A[0]),
+               dict(A=A.T), dict(A=T.ones((4, 6), dtype=T.float64, device="cuda"), m=None), dict(A=A[:0]),
+               dict(out=out.float()), dict(out=out.cpu()), dict(out=out[:3]), dict(out=out.T), dict(out=A[:, :3]),
+               dict(out=T.full((3, 4), -7.0, dtype=T.float64, device="cuda").T)):
+        args = dict(A=A, B=B, m=3, out=out)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            engine.gram_rows(ctx, args.pop("A"), args.pop("B"), args.pop("m"), out=args.pop("out"))
+    with pytest.raises(ValueError, match="overlaps"):
+        engine.gram_rows(ctx, A, None, 1, out=A[:, 4:8])
+    T.cuda.synchronize()
+    assert bool((out == -7.0).all()) and bool((A == 1.0).all())
+
+
+# ----------------------------------------------------------------------------- 5. against the oracle
+def _moment_band(ref_a, ref_b, tol, n):
+    """|sum (a + da)(b + db) - sum a b| with |da|, |db| <= tol per entry, n entries."""
+    return tol * (np.abs(ref_a).sum() + np.abs(ref_b).sum()) + n * tol * tol
+
+
+def _log2_band(coll, d_coll, mass, d_mass):
+    """|log2((c + dc) / (m + dm)^2) - log2(c / m^2)|: |ln(1 + x)| <= 2 |x| for |x| <= 1/2."""
+    x = d_coll / coll + 2 * d_mass / abs(mass) + (d_mass / mass) ** 2
+    assert x <= 0.5
+    return 2 * x / math.log(2)
+
+
+@pytest.mark.parametrize("case,factored", [(c, f) for c in sorted(CASES) for f in (False, True)
+                                           if not (f and c in DIRECT_ONLY)])
+def test_collision_probability_matches_the_oracle(T, case, factored):
+    cut, ref = _case(case)
+    virt = VirtualCircuit(cut)
+    N = virt.circuit.num_clbits
+    assert N <= 13
+    red = KnitReducer(virt, factored=factored)
+    assert red.factored == factored
+    got = red.collision_probability()
+    want = float((ref * ref).sum())
+    band = _moment_band(ref, ref, TOL, 1 << N)
+    print(f"{case} factored={factored}: collision {got:.12g}, oracle {want:.12g}, {abs(got - want) / band:.3g} of the band")
+    assert isinstance(got, float) and abs(got - want) <= band
+    assert red.collision_probability() == got and red.overlap() == got and red.overlap(red) == got
+    assert red.collision_probability(list(range(N))) == got
+    # entropy and ideal XEB from the same numbers
+    mass, d_mass = float(ref.sum()), (1 << N) * TOL
+    measured = sorted(c for cl in red.clbits for c in cl)
+    D = 2.0 ** len(measured)
+    assert abs(red.ideal_xeb() - (D * want - 1)) <= D * band
+    assert abs(red.renyi2_entropy() + math.log2(want / mass ** 2)) <= _log2_band(want, band, mass, d_mass)
+    if case == "extra_clbit":  # the clbits nobody measures change nothing
+        assert measured == [0, 2, 4]
+        assert red.collision_probability(measured) == got and red.collision_probability([4, 3, 0, 1, 2]) == got
+        assert red.ideal_xeb(measured) == red.ideal_xeb()
+        assert abs(red.collision_probability([1, 3]) - mass ** 2) <= 2 * abs(mass) * d_mass + d_mass ** 2
+
+
+@pytest.mark.parametrize("case", ["cx_wide", "three_wide", "interleaved", "extra_clbit", "partial"])
+def test_moments_over_chosen_clbits_are_those_of_the_marginal(T, case):
+    """A set that straddles the cut, in non-ascending order. An entry of a marginal sums up to 2^N entries of the
+    knit, so it carries 2^N * 1e-12."""
+    cut, ref = _case(case)
+    virt = VirtualCircuit(cut)
+    N = virt.circuit.num_clbits
+    red = KnitReducer(virt)
+    fcl = [cl for cl in red.clbits if cl]
+    assert len(fcl) >= 2
+    straddle = sorted({fcl[0][0], fcl[0][-1], fcl[1][0], fcl[-1][-1]}, reverse=True)
+    assert straddle != sorted(straddle)
+    tol = (1 << N) * TOL
+    mass = float(ref.sum())
+    for clbits in (straddle, straddle[:1], []):
+        marg = np_marginal(ref, clbits)
+        want = float((marg * marg).sum())
+        band = _moment_band(marg, marg, tol, marg.size)
+        got = red.collision_probability(clbits)
+        assert abs(got - want) <= band, clbits
+        assert red.collision_probability(sorted(clbits)) == got == red.collision_probability(clbits)
+        D = 2.0 ** sum(1 for c in clbits if any(c in cl for cl in red.clbits))
+        assert abs(red.ideal_xeb(clbits) - (D * want - 1)) <= D * band
+        assert abs(red.renyi2_entropy(clbits) + math.log2(want / mass ** 2)) <= _log2_band(want, band, mass, tol)
+    # mutual information between the two halves of the straddling set
+    a, b = straddle[:2], straddle[2:] or [c for c in fcl[-1] if c not in straddle][:1]
+    parts = {}
+    for key, cl in (("a", a), ("b", b), ("ab", a + b)):
+        marg = np_marginal(ref, cl)
+        coll = float((marg * marg).sum())
+        parts[key] = (-math.log2(coll / mass ** 2), _log2_band(coll, _moment_band(marg, marg, tol, marg.size), mass, tol))
+    want = parts["a"][0] + parts["b"][0] - parts["ab"][0]
+    assert abs(red.mutual_information2(a, b) - want) <= sum(p[1] for p in parts.values())
+    with pytest.raises(ValueError, match="both"):
+        red.mutual_information2(a, a)
+    with pytest.raises(ValueError, match="duplicate"):
+        red.collision_probability([0, 0])
+    with pytest.raises(ValueError, match="outside"):
+        red.overlap(None, [N])
+
+
+# ----------------------------------------------------------------------------- 6. two reducers
+INTERLEAVED = {0: 0, 1: 2, 2: 1, 3: 3}  # fragment clbits [0, 2] and [1, 3]
+STRAIGHT = {0: 0, 1: 1, 2: 2, 3: 3}     # fragment clbits [0, 1] and [2, 3]
+
+
+@functools.lru_cache(maxsize=None)
+def _pair(seed, straight=False):
+    _, cut = obs_cases._two_by_two(seed, 4, STRAIGHT if straight else INTERLEAVED)
+    ref = dense.run_dense(cut)
+    ref.setflags(write=False)
+    return cut, ref
+
+
+def _abs_rows(red, clbits):
+    """Per fragment (|W| [swept rows, K], |q| summed onto the kept clbits [swept rows, 2^k])."""
+    Ws = engine.plan_transforms(red.ops, red.frags)
+    out = []
+    for W, q, fcl in zip(Ws, red.qs, red.clbits):
+        kept = [i for i, c in enumerate(fcl) if c in clbits]
+        q = np.abs(q.cpu().numpy())
+        out.append((np.abs(W), np.stack([np_marginal(row, kept) for row in q])))
+    return out
+
+
+def _swap_band(a, b, clbits):
+    """Bound on |a.overlap(b) - b.overlap(a)| from rounding alone. Both evaluate
+    sum_{k,k'} prod_f (W_f^T (q_f q'_f^T) W'_f)[k,k']; with S the same expression on absolute values and n the
+    roundings on the way to one term and through the sums (per fragment at most 2^m_f in reduce + Gram,
+    R_f + R'_f in the two transforms, 2 for gather coefficients; F - 1 for the product; K K' for the sums), each is
+    within n 2^-53 S of the exact value to first order (n 2^-53 < 1e-11: 1 % covers the higher orders)."""
+    ra, rb = _abs_rows(a, clbits), _abs_rows(b, clbits)
+    Ka, Kb = a.ops.num_terms, b.ops.num_terms
+    pairs, only_a, only_b = match_fragments(a.clbits, b.clbits, clbits)
+    S, n = np.ones((Ka, Kb)), Ka * Kb + len(a.clbits) + len(b.clbits)
+    for f, g, _ in pairs:
+        S = S * (ra[f][0].T @ (ra[f][1] @ rb[g][1].T) @ rb[g][0])
+        n += (1 << len(a.clbits[f])) + ra[f][1].shape[0] + rb[g][1].shape[0] + 2
+    for f in only_a:
+        S = S * (ra[f][0].T @ ra[f][1])  # [Ka, 1]
+        n += (1 << len(a.clbits[f])) + ra[f][1].shape[0] + 2
+    for g in only_b:
+        S = S * (rb[g][0].T @ rb[g][1]).T
+        n += (1 << len(b.clbits[g])) + rb[g][1].shape[0] + 2
+    return 2 * 1.01 * n * EPS * float(S.sum())
+
+
+@pytest.mark.parametrize("factored", [False, True])
+def test_overlap_and_distance_of_two_knits(T, factored):
+    (cut_a, ref_a), (cut_b, ref_b) = _pair(22), _pair(23)
+    a = KnitReducer(VirtualCircuit(cut_a), factored=factored)
+    b = KnitReducer(VirtualCircuit(cut_b), factored=factored)
+    assert a.clbits == [[0, 2], [1, 3]] == b.clbits
+    band = _moment_band(ref_a, ref_b, TOL, 16)
+    want = float((ref_a * ref_b).sum())
+    ab, ba = a.overlap(b), b.overlap(a)
+    print(f"factored={factored}: overlap {ab:.12g}, oracle {want:.12g}, {abs(ab - want) / band:.3g} of the band")
+    assert abs(ab - want) <= band and abs(ba - want) <= band and a.overlap(b) == ab
+    swap = _swap_band(a, b, [0, 1, 2, 3])
+    print(f"factored={factored}: |overlap(a, b) - overlap(b, a)| = {abs(ab - ba):.3g}, rounding band {swap:.3g}")
+    assert abs(ab - ba) <= swap
+    s_aa, s_bb = a.collision_probability(), b.collision_probability()
+    floor = math.sqrt(2.0 ** -52 * (s_aa + s_bb))
+    dist = a.l2_distance(b)
+    print(f"factored={factored}: distance {dist:.12g}, oracle {np.linalg.norm(ref_a - ref_b):.12g}, floor {floor:.3g}")
+    assert abs(dist - np.linalg.norm(ref_a - ref_b)) <= floor
+    assert abs(b.l2_distance(a) - dist) <= floor
+    assert a.l2_distance(a) <= floor
+    # chosen clbits, one from each fragment, not ascending; a mixed pair of a direct and a factored reducer
+    ma, mb = np_marginal(ref_a, [3, 0]), np_marginal(ref_b, [3, 0])
+    assert abs(a.overlap(b, [3, 0]) - float((ma * mb).sum())) <= _moment_band(ma, mb, 16 * TOL, 4)
+    assert abs(a.overlap(b, [3, 0]) - b.overlap(a, [3, 0])) <= _swap_band(a, b, [3, 0])
+    other = KnitReducer(VirtualCircuit(cut_b), factored=not factored)
+    assert abs(a.overlap(other) - want) <= band
+    assert abs(a.overlap(other) - other.overlap(a)) <= _swap_band(a, other, [0, 1, 2, 3])
+
+
+def test_overlap_needs_the_same_partition_of_the_chosen_clbits(T):
+    (cut_a, ref_a), (cut_b, ref_b) = _pair(22), _pair(23, straight=True)
+    a, b = KnitReducer(VirtualCircuit(cut_a)), KnitReducer(VirtualCircuit(cut_b))
+    assert a.clbits == [[0, 2], [1, 3]] and b.clbits == [[0, 1], [2, 3]]
+    for clbits in (None, [0, 1], [1, 0], [0, 1, 2, 3]):
+        with pytest.raises(ValueError, match="differently"):
+            a.overlap(b, clbits)
+        with pytest.raises(ValueError, match="differently"):
+            b.l2_distance(a, clbits)
+    with pytest.raises(ValueError):
+        match_fragments(a.clbits, b.clbits, [0, 1])
+    for clbits in ([0, 3], [3, 0], [2], []):
+        ma, mb = np_marginal(ref_a, clbits), np_marginal(ref_b, clbits)
+        got = a.overlap(b, clbits)
+        assert abs(got - float((ma * mb).sum())) <= _moment_band(ma, mb, 16 * TOL, ma.size), clbits
+        assert abs(b.overlap(a, clbits) - got) <= _swap_band(a, b, clbits), clbits
+    # different clbit counts
+    five = KnitReducer(VirtualCircuit(_case("extra_clbit")[0]))
+    assert five.N == 5
+    with pytest.raises(ValueError, match="clbits against"):
+        a.overlap(five)
+    with pytest.raises(ValueError, match="clbits against"):
+        five.l2_distance(a, [0])
+    with pytest.raises(ValueError, match="KnitReducer"):
+        a.overlap(ref_a)
+    with pytest.raises(ValueError, match="KnitReducer"):
+        a.l2_distance(ref_a)
+
+
+def test_overlap_of_sides_permutes_a_differing_local_bit_order(T):
+    """Hand-built sides whose paired fragments hold the same clbits in another local order and in another
+    position, one side by gathers and one by a transform, against second_moment_host on the re-ordered rows;
+    the band is that of _swap_band: n roundings on the sum of absolute terms."""
+    ctx = engine.get_context(0)
+    rng = np.random.default_rng(5)
+    Ka, Kb = 5, 7
+    cla, clb = [[0, 2, 5], [1, 3]], [[3, 1], [5, 0, 2], [4]]
+    qa = [rng.standard_normal((4, 8)), rng.standard_normal((3, 4))]
+    qb = [rng.standard_normal((6, 4)), rng.standard_normal((2, 8)), rng.standard_normal((3, 2))]
+    idx, coef = [rng.integers(0, q.shape[0], Ka) for q in qa], [rng.standard_normal(Ka) for _ in qa]
+    Wb = [rng.standard_normal((Kb, q.shape[0])) for q in qb]
+    dev = lambda x: T.from_numpy(np.ascontiguousarray(x)).cuda()
+    side_a = ([dev(q) for q in qa], [("G", dev(i), dev(c)) for i, c in zip(idx, coef)], cla, Ka)
+    side_b = ([dev(q) for q in qb], [("T", dev(W.T)) for W in Wb], clb, Kb)
+    kept = [0, 1, 2, 3, 5]  # clbit 4 is not kept: b's third fragment is summed out before it gets here
+    side_b[0][2] = side_b[0][2].sum(dim=1, keepdim=True)
+    pairs, only_a, only_b = match_fragments(cla, clb, kept)
+    assert pairs == [(0, 1, [1, 2, 0]), (1, 0, [1, 0])] and only_a == [] and only_b == [2]
+
+    def reorder(q, mine, theirs):  # columns of q (bit i = mine[i]) re-indexed so that bit i = theirs[i]
+        y = np.arange(q.shape[1])
+        old = np.zeros_like(y)
+        for i, c in enumerate(theirs):
+            old |= ((y >> i) & 1) << mine.index(c)
+        return q[:, old]
+
+    Xa = [c[:, None] * q[i] for q, i, c in zip(qa, idx, coef)] + [np.ones((Ka, 1))]
+    Xb = [Wb[1] @ reorder(qb[1], clb[1], cla[0]), Wb[0] @ reorder(qb[0], clb[0], cla[1]),
+          Wb[2] @ qb[2].sum(axis=1, keepdims=True)]
+    want = second_moment_host(Xa, Xb)
+    Aa = [np.abs(c)[:, None] * np.abs(q[i]) for q, i, c in zip(qa, idx, coef)] + [np.ones((Ka, 1))]
+    Ab = [np.abs(Wb[1]) @ np.abs(reorder(qb[1], clb[1], cla[0])), np.abs(Wb[0]) @ np.abs(reorder(qb[0], clb[0], cla[1])),
+          np.abs(Wb[2]) @ np.abs(qb[2]).sum(axis=1, keepdims=True)]
+    band = 1.01 * (Ka * Kb + 3 * (8 + 6 + 2) + 3) * EPS * float(second_moment_host(Aa, Ab))
+    got = overlap_of_sides(ctx, side_a, side_b, kept)
+    print(f"permuted sides: {got:.15g} against {float(want):.15g}, {abs(got - float(want)) / band:.3g} of the band")
+    assert abs(got - want) <= band
+    assert abs(overlap_of_sides(ctx, side_b, side_a, kept) - want) <= band
+    # the same order on both sides needs no permutation and gives the same number to rounding
+    same_b = ([dev(reorder(qb[1], clb[1], cla[0])), dev(reorder(qb[0], clb[0], cla[1])), side_b[0][2]],
+              [side_b[1][1], side_b[1][0], side_b[1][2]], [cla[0], cla[1], [4]], Kb)
+    assert match_fragments(cla, same_b[2], kept)[0] == [(0, 0, None), (1, 1, None)]
+    assert overlap_of_sides(ctx, side_a, same_b, kept) == got
+
+
+# ----------------------------------------------------------------------------- 7. entry points, the empty case
+def test_collision_and_overlap_entry_points(T):
+    (cut_a, _), (cut_b, _) = _pair(22), _pair(23)
+    va, vb = VirtualCircuit(cut_a), VirtualCircuit(cut_b)
+    a, b = KnitReducer(va), KnitReducer(vb)
+    value, info = run_virtual_circuit_collision(va)
+    assert isinstance(value, float) and value == a.collision_probability()
+    assert isinstance(info, RunTimeInfo) and info.run_time > 0 and info.knit_time > 0
+    value, _ = run_virtual_circuit_collision(va, [3, 0], factored=False)
+    assert value == KnitReducer(va, factored=False).collision_probability([3, 0])
+    value, info = run_virtual_circuit_overlap(va, vb)
+    assert isinstance(value, float) and value == a.overlap(b)
+    assert isinstance(info, RunTimeInfo) and info.run_time > 0 and info.knit_time > 0
+    value, _ = run_virtual_circuit_overlap(va, vb, [2])
+    assert value == a.overlap(b, [2])
+    for call in (lambda **kw: run_virtual_circuit_collision(va, **kw), lambda **kw: run_virtual_circuit_overlap(va, vb, **kw)):
+        with pytest.raises(ValueError, match="exact"):
+            call(sample=True)
+        with pytest.raises(ValueError, match="one GPU"):
+            call(group="WORLD")
+
+
+def test_no_fragment_at_all_gives_the_scalar_squared(T):
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.circuit import (ClassicalRegister, QuantumCircuit,
+                                                                                  QuantumRegister)
+
+    virt = VirtualCircuit(QuantumCircuit(QuantumRegister(0, "q"), ClassicalRegister(3, "c")))
+    red = KnitReducer(virt)
+    assert not red.frags
+    assert red.collision_probability() == red._scalar ** 2 == red.overlap(red, [2, 0])
+    assert red.ideal_xeb() == red._scalar ** 2 - 1
+    value, info = run_virtual_circuit_collision(virt)
+    assert value == red._scalar ** 2 and isinstance(info, RunTimeInfo)
+
+
+# ----------------------------------------------------------------------------- 8. wide output
+@pytest.mark.slow
+def test_wide_output_36_clbits_collision_probability(T):
+    """hwe 36 in two 18-qubit fragments: sum_x R[x]^2 over 2^36 outcomes against
+    sum_{k,k'} c_k c_k' (q0 q0^T)[k,k'] (q1 q1^T)[k,k'] from the oracle's rows; a Gram entry is a dot product of
+    2^18 terms, hence the relative band 2^18 * 2^-52."""
+    _, cut, _ = cutting.config_cut_circuit("hwe", 36, 1, 2)
+    view = qvm.CutView(cut)
+    (kind, params, _, _), = view.vgates
+    coef = np.asarray(tables.coefficients(kind, params))
+    rows = [dense.fragment_q(view, list(qreg)) for qreg in view.qregs if len(qreg)]
+    assert [len(cl) for _, cl in rows] == [18, 18] and all(q.shape[0] == coef.size for q, _ in rows)
+    (q0, _), (q1, _) = rows
+    want = float((np.outer(coef, coef) * (q0 @ q0.T) * (q1 @ q1.T)).sum())
+
+    virt = VirtualCircuit(cut)
+    T.cuda.synchronize()
+    T.cuda.reset_peak_memory_stats()
+    got, info = run_virtual_circuit_collision(virt)
+    T.cuda.synchronize()
+    peak = T.cuda.max_memory_allocated()
+    print(f"collision {got:.12g} (oracle {want:.12g}, relative deviation {abs(got - want) / want:.3g}), ideal XEB "
+          f"{2.0 ** 36 * got - 1:.4f}, peak device memory {peak / 2**20:.1f} MiB, sweep {info.run_time * 1e3:.1f} ms, "
+          f"moments {info.knit_time * 1e3:.1f} ms")
+    assert peak < 4 << 30
+    assert abs(got - want) <= 2.0 ** 18 * 2.0 ** -52 * want

@@ -22,7 +22,10 @@ expectation(method="reduce") for 16, 64 and 1024, and the smallest measured M at
 route with its one-off cost wins.
 
 ``--lookup`` runs the probabilities-at-chosen-keys leg instead (``--out``: e.g.
-profiles/obs_bench_lookup.json): see lookup_leg."""
+profiles/obs_bench_lookup.json): see lookup_leg.
+
+``--moments`` runs the second-moments leg instead (``--out``: e.g. profiles/obs_bench_moments.json): see
+moments_leg."""
 import argparse
 import glob
 import json
@@ -306,8 +309,83 @@ def lookup_leg(args):
             fh.write("\n")
 
 
+def moments_leg(args):
+    """Second moments (``--out``: e.g. profiles/obs_bench_moments.json): (a) qk_gram_rows alone on each
+    fragment's swept rows of syc 32 5 (the symmetric call, as collision_probability makes it, and the
+    two-operand call on a copy), with the bytes it has to read and the flops it issues; (b)
+    KnitReducer.collision_probability() end to end; (c) torch's ``A @ A.T`` on the same rows in the same process;
+    (d) the only other route to the number: the dense step plus ``(R * R).sum()`` over its 2^32 output."""
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine, observables as ob
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.run import run_virtual_circuit_dense
+
+    res = {"config": "syc_32_5_p2", "device": torch.cuda.get_device_name(0), "reps": 20}
+    _, cut, _ = cutting.config_cut_circuit("syc", 32, 5, 2)
+    virt = VirtualCircuit(cut)
+    red = KnitReducer(virt)
+    ctx = engine.get_context(0)
+    res["fragments"] = [{"rows": int(q.shape[0]), "m": len(cl)} for q, cl in zip(red.qs, red.clbits)]
+    res["terms"] = int(red.ops.num_terms)
+
+    for q, cl in zip(red.qs, red.clbits):
+        R, m = int(q.shape[0]), len(cl)
+        sh = ob.gram_split(R, R, m)
+        G, copy = torch.empty((R, R), dtype=torch.float64, device="cuda"), q.clone()
+        blocks = sh["ba"] * sh["bb"]
+        entry = {"rows": R, "m": m, "split": sh["split"], "workgroups": blocks * sh["split"],
+                 "workspace_bytes": sh["workspace_bytes"], "source_bytes": R * (8 << m),
+                 "mfma_flops": 2 * (blocks * 64 * 64) * (1 << m)}
+        for name, fn in (("symmetric", lambda: engine.gram_rows(ctx, q, None, m, out=G)),
+                         ("two_operands", lambda: engine.gram_rows(ctx, q, copy, m, out=G))):
+            t = timed(torch, fn)
+            # a diagonal block reads its rows once, every other block both row sets
+            diag = min(sh["ba"], sh["bb"]) if name == "symmetric" else 0
+            t["bytes_read"] = (2 * blocks - diag) * 64 * (8 << m) + sh["workspace_bytes"]
+            t["bytes_written"] = sh["workspace_bytes"] + R * R * 8
+            t["GBs"] = (t["bytes_read"] + t["bytes_written"]) / t["median_ms"] / 1e6
+            t["TFLOPs"] = entry["mfma_flops"] / t["median_ms"] / 1e9
+            entry[name] = t
+        entry["torch_A_At"] = timed(torch, lambda: torch.matmul(q, q.T, out=G))
+        entry["torch_A_Bt"] = timed(torch, lambda: torch.matmul(q, copy.T, out=G))
+        # a single call is a few launches long: 50 calls between one pair of events, per call
+        for name, fn in (("symmetric_50_calls", lambda: engine.gram_rows(ctx, q, None, m, out=G)),
+                         ("torch_A_At_50_calls", lambda: torch.matmul(q, q.T, out=G))):
+            t = timed(torch, lambda: [fn() for _ in range(50)])
+            entry[name] = {k: v / 50 for k, v in t.items()}
+        entry["kernel_over_torch_symmetric"] = entry["symmetric"]["median_ms"] / entry["torch_A_At"]["median_ms"]
+        entry["kernel_over_torch_two_operands"] = entry["two_operands"]["median_ms"] / entry["torch_A_Bt"]["median_ms"]
+        entry["max_abs_diff_vs_torch"] = float((engine.gram_rows(ctx, q, None, m) - q @ q.T).abs().max())
+        res[f"qk_gram_rows_{R}x2^{m}"] = entry
+
+    res["collision_probability"] = timed(torch, lambda: red.collision_probability())
+    res["collision"] = red.collision_probability()
+    res["ideal_xeb"] = red.ideal_xeb()
+    res["renyi2_entropy_bits"] = red.renyi2_entropy()
+    half = [c for cl in red.clbits for c in cl[:len(cl) // 2]]
+    res["collision_probability_16_clbits"] = timed(torch, lambda: red.collision_probability(half))
+    if not args.no_dense:
+        torch.cuda.empty_cache()
+
+        def dense_collision():
+            full, _ = run_virtual_circuit_dense(virt)
+            return float((full * full).sum())
+
+        res["check"] = {"collision_vs_dense_abs_diff": abs(dense_collision() - res["collision"])}
+        res["dense_step_only"] = timed(torch, lambda: run_virtual_circuit_dense(virt))
+        res["dense_step_sum_of_squares"] = timed(torch, dense_collision)
+    print(json.dumps(res, indent=1), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--moments", action="store_true", help="the second-moments leg only (see moments_leg)")
     ap.add_argument("--lookup", action="store_true", help="the probabilities-at-chosen-keys leg only (see lookup_leg)")
     ap.add_argument("--spectrum", action="store_true", help="the Walsh-Hadamard spectrum leg only (see spectrum_leg)")
     ap.add_argument("--out", default=None)
@@ -323,6 +401,8 @@ def main():
         return spectrum_leg(args)
     if args.lookup:
         return lookup_leg(args)
+    if args.moments:
+        return moments_leg(args)
     import torch
 
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
