@@ -1074,18 +1074,28 @@ OUTER_STREAM_KERNELS = ("qk_knit_outer_stream_kernel", "qk_knit_outer_blocked_ke
                         "qk_knit_outer_blocked_kernel<b_global>", "qk_knit_outer_rows_kernel")
 
 
-def knit_outer_stream_kernel(K: int, clbits_a: list, clbits_b: list, nbits: int, o_begin: int = 0,
-                             o_count: int | None = None) -> str:
-    """Name of the kernel :func:`knit_outer_stream` launches for these arguments
-    (``qk_knit_outer_stream_kind``): the per-output gather, the blocked kernel with both operands
-    staged in LDS, or the blocked kernel reading B from global memory."""
+def knit_outer_stream_kind(K: int, clbits_a: list, clbits_b: list, nbits: int, o_begin: int = 0,
+                           o_count: int | None = None) -> tuple:
+    """``(kind, task_bits)`` of the kernel :func:`knit_outer_stream` launches for these arguments
+    (``qk_knit_outer_stream_kind``; no launch, no device needed). ``kind`` indexes
+    :data:`OUTER_STREAM_KERNELS`; ``task_bits`` is log2 of the outputs per task (blocked kernels) or
+    piece (rows kernel), 0 for the per-output gather."""
     mA, mB = sum(1 << c for c in clbits_a), sum(1 << c for c in clbits_b)
     if o_count is None:
         o_count = (1 << nbits) - o_begin
     kind, tb = ctypes.c_int(), ctypes.c_int()
     _lib.check(None, _lib.lib().qk_knit_outer_stream_kind(nbits, K, mA, mB, o_begin, o_count, ctypes.byref(kind),
                                                           ctypes.byref(tb)), "qk_knit_outer_stream_kind")
-    return OUTER_STREAM_KERNELS[kind.value]
+    return kind.value, tb.value
+
+
+def knit_outer_stream_kernel(K: int, clbits_a: list, clbits_b: list, nbits: int, o_begin: int = 0,
+                             o_count: int | None = None) -> str:
+    """Name of the kernel :func:`knit_outer_stream` launches for these arguments
+    (:func:`knit_outer_stream_kind`): the per-output gather, the blocked kernel with both operands
+    staged in LDS, the blocked kernel reading B from global memory, or the rows kernel holding B runs
+    in registers (B holds the low output bits and the range is piece-aligned)."""
+    return OUTER_STREAM_KERNELS[knit_outer_stream_kind(K, clbits_a, clbits_b, nbits, o_begin, o_count)[0]]
 
 
 def stream_knit_ok(clbits_a: list, clbits_b: list, nbits: int) -> bool:

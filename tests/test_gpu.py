@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import circuits
+import knit_write_cases
 import zoo_cases as zoo
 from oracle import dense, qvm
 
@@ -1108,14 +1109,17 @@ def test_syc_32_1_fragment_rows_match_oracle(T, variant):
 def test_knit_outer_stream_matches_torch(T, K, nbits, bits_b):
     """qk_knit_outer_stream: the small-K two-fragment knit written in output order equals A^T B
     scattered through the deposit keys of the two clbit sets. nbits 3: the per-output kernel on a
-    single partial chunk (8 outputs, grid of 1); nbits >= 9: the blocked kernel (tasks of 2^TB
-    outputs, TB <= 16, the operand stage in LDS); nbits 18 / K 8 / 14 low B bits: the B range of a
-    task is too large to stage, the blocked kernel reads B from global memory (syc 32 1's layout)."""
+    single partial chunk (8 outputs, grid of 1); nbits 9..17: the blocked kernel (tasks of 2^TB
+    outputs, TB <= 16, the operand stage in LDS); nbits 18 / K 8 / 14 low B bits: B holds the low
+    output bits, so the rows kernel <8,11> writes it (pieces of 2^11 outputs, B runs in registers).
+    The kernel each case takes is asserted from the table shared with tests/test_gpu_knit_write.py,
+    which covers the blocked kernel reading B from global memory and the other rows instantiations."""
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.knit_plan import deposit_keys
 
     ctx = engine.get_context(0)
     bits_a = [b for b in range(nbits) if b not in bits_b]
     assert engine.stream_knit_ok(bits_a, bits_b, nbits)
+    assert engine.knit_outer_stream_kind(K, bits_a, bits_b, nbits) == knit_write_cases.LEGACY[K, nbits, tuple(bits_b)]
     M, N = 1 << len(bits_a), 1 << len(bits_b)
     g = T.Generator(device="cuda").manual_seed(29 + K)
     A = T.randn(K, M, dtype=T.float64, device="cuda", generator=g)
@@ -1138,6 +1142,8 @@ def test_knit_outer_stream_range_slices_and_device_k(T):
     nbits, K = 18, 3
     bits_b = [0, 1, 2, 3, 8, 9, 10, 11, 16, 17]
     bits_a = [b for b in range(nbits) if b not in bits_b]
+    assert engine.knit_outer_stream_kind(K, bits_a, bits_b, nbits) == knit_write_cases.LEGACY[K, nbits, tuple(bits_b)]
+    assert engine.knit_outer_stream_kind(K, bits_a, bits_b, nbits, 1 << 16, 1 << 16) == (1, 16)
     g = T.Generator(device="cuda").manual_seed(5)
     A = T.randn(K, 1 << len(bits_a), dtype=T.float64, device="cuda", generator=g)
     B = T.randn(K, 1 << len(bits_b), dtype=T.float64, device="cuda", generator=g)
@@ -1467,6 +1473,7 @@ def test_knit_select_matches_dense_threshold(T, K, nbits, bits_b, frac):
     a capacity too small at first is detected and the call repeated with room."""
     ctx = engine.get_context(0)
     bits_a = [b for b in range(nbits) if b not in bits_b]
+    assert engine.knit_outer_stream_kind(K, bits_a, bits_b, nbits) == knit_write_cases.LEGACY[K, nbits, tuple(bits_b)]
     M, N = 1 << len(bits_a), 1 << len(bits_b)
     g = T.Generator(device="cuda").manual_seed(101 + K)
     A = T.randn(K, M, dtype=T.float64, device="cuda", generator=g)
