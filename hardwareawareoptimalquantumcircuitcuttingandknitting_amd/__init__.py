@@ -28,8 +28,9 @@ from .virtual_gates import (
 )
 from .virtual_circuit import VirtualCircuit, generate_instantiations
 from .run import (RunTimeInfo, run_virtual_circuit, run_virtual_circuit_collision, run_virtual_circuit_dense,
-                  run_virtual_circuit_expectation, run_virtual_circuit_marginal, run_virtual_circuit_overlap,
-                  run_virtual_circuit_probabilities, run_virtual_circuit_shots, run_virtual_circuit_xeb)
+                  run_virtual_circuit_expectation, run_virtual_circuit_fidelity, run_virtual_circuit_marginal,
+                  run_virtual_circuit_overlap, run_virtual_circuit_probabilities, run_virtual_circuit_scan,
+                  run_virtual_circuit_shots, run_virtual_circuit_top_k, run_virtual_circuit_xeb)
 
 __all__ = [
     "ClassicalRegister", "QuantumCircuit", "QuantumRegister", "QuasiDistr", "RZZ_ACCURACY",
@@ -38,5 +39,6 @@ __all__ = [
     "generate_instantiations", "RunTimeInfo", "run_virtual_circuit", "run_virtual_circuit_dense",
     "run_virtual_circuit_marginal", "run_virtual_circuit_expectation", "run_virtual_circuit_shots",
     "run_virtual_circuit_probabilities", "run_virtual_circuit_xeb", "run_virtual_circuit_collision",
-    "run_virtual_circuit_overlap",
+    "run_virtual_circuit_overlap", "run_virtual_circuit_scan", "run_virtual_circuit_top_k",
+    "run_virtual_circuit_fidelity",
 ]

@@ -150,6 +150,11 @@ SIGNATURES = {
                            ctypes.POINTER(ctypes.c_int), c_vp, c_i64, c_u64, c_vp]),
     "qk_gram_rows_workspace_bytes": (c_i32, [c_i64, c_i64, ctypes.c_int, ctypes.POINTER(c_i64)]),
     "qk_gram_rows": (c_i32, [c_vp, c_i64, c_i64, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]),
+    "qk_knit_scan_workspace_bytes": (c_i32, [ctypes.c_int, ctypes.c_int, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "qk_knit_scan": (c_i32, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
+                             c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "qk_knit_collect": (c_i32, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                ctypes.c_double, c_i64, c_vp, c_vp, c_vp]),
 }
 
 _lock = threading.Lock()

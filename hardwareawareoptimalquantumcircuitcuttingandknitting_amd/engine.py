@@ -872,6 +872,124 @@ def gram_rows(ctx: Context, A, B=None, m: int | None = None, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- the streamed scan
+SCAN_SLAB_OUTPUTS = 1 << 34  # outputs per qk_knit_scan / qk_knit_collect launch: side A is walked in slabs
+SCAN_BINS = 128  # QK_SCAN_BINS
+SCAN_STATS = ("sum", "abs", "pos", "sq", "ent", "max", "min", "sum2", "pos2", "cross", "hell", "l1d", "maxd")  # QK_SCAN_*
+_SCAN_NSTATS, _SCAN_NCOUNTS, _SCAN_ENTROPY = 16, 4, 1
+
+
+def _scan_side(name: str, X, K: int | None = None):
+    """``(K, m, ld)`` of a scan operand: a device float64 ``[K, 2^m]`` with unit column stride."""
+    T = torch()
+    if X.dim() != 2 or X.dtype != T.float64 or not X.is_cuda or X.shape[0] < 1 or X.shape[1] < 1 or (
+            X.shape[1] > 1 and X.stride(1) != 1):
+        raise ValueError(f"{name} must be a device float64 [K >= 1, 2^m] with unit column stride")
+    cols = X.shape[1]
+    if cols & (cols - 1) or cols > 1 << 30:
+        raise ValueError(f"{name} has {cols} columns, not a power of two up to 2^30")
+    if K is not None and X.shape[0] != K:
+        raise ValueError(f"{name} has {X.shape[0]} rows for {K} terms")
+    ld = X.stride(0) if X.shape[0] > 1 else max(X.stride(0), cols)
+    if ld < cols:
+        raise ValueError(f"row stride of {name} below its {cols} columns")
+    return X.shape[0], cols.bit_length() - 1, ld
+
+
+def scan_slabs(ma: int, mb: int) -> list:
+    """The ``[i_begin, i_end)`` ranges of side A that the scan walks: at most ``SCAN_SLAB_OUTPUTS`` outputs each."""
+    rows = max(1, SCAN_SLAB_OUTPUTS >> mb)
+    return [(i, min(i + rows, 1 << ma)) for i in range(0, 1 << ma, rows)]
+
+
+def knit_scan(ctx: Context, A, B, A2=None, B2=None, *, tau: float = 0.0, entropy: bool = False, hist: bool = False) -> dict:
+    """``qk_knit_scan``: statistics of ``R[i][j] = sum_k A[k, i] B[k, j]`` (flat index ``i << mb | j``) without
+    forming it. ``A [K, 2^ma]``, ``B [K, 2^mb]``: device float64 with unit column stride, only read; ``A2`` /
+    ``B2``: a second knit ``R'`` on the same outputs (any number of terms), or ``None``. Returns a dict of Python
+    floats named as ``SCAN_STATS`` (``ent`` only with ``entropy=True``, the pair statistics only with a second
+    knit; else 0.0), the ints ``count_tau`` (``R > tau``, strict), ``count_pos``, ``argmax``, ``argmin`` (flat
+    indices, the lowest among equal values) and ``hist`` (numpy int64 ``[128]``, bin ``clamp(-ilogb(p), 0, 127)`` of
+    every ``p > 0``; ``None`` without ``hist=True``). Side A is walked in slabs of at most ``SCAN_SLAB_OUTPUTS``
+    outputs; the slabs' statistics are combined in ascending order in float64 on the host."""
+    T = torch()
+    K, ma, lda = _scan_side("A", A)
+    _, mb, ldb = _scan_side("B", B, K)
+    pair = A2 is not None or B2 is not None
+    K2 = lda2 = ldb2 = 0
+    if pair:
+        if A2 is None or B2 is None:
+            raise ValueError("a second knit needs both A2 and B2")
+        K2, ma2, lda2 = _scan_side("A2", A2)
+        _, mb2, ldb2 = _scan_side("B2", B2, K2)
+        if (ma2, mb2) != (ma, mb) or A2.device != A.device or B2.device != A.device:
+            raise ValueError(f"the second knit is 2^{ma2} x 2^{mb2}, the first 2^{ma} x 2^{mb} (or another device)")
+    if B.device != A.device:
+        raise ValueError("A and B must be on one device")
+    tau = float(tau)
+    if tau != tau:
+        raise ValueError("tau is not a number")
+    slabs = scan_slabs(ma, mb)
+    dev = A.device
+    stats = T.empty((len(slabs), _SCAN_NSTATS), dtype=T.float64, device=dev)
+    counts = T.empty((len(slabs), _SCAN_NCOUNTS), dtype=T.int64, device=dev)
+    hists = T.empty((len(slabs), SCAN_BINS), dtype=T.int64, device=dev) if hist else None
+    need = ctypes.c_int64()
+    ctx.check(ctx.lib.qk_knit_scan_workspace_bytes(ma, mb, *slabs[0], ctypes.byref(need)), "qk_knit_scan_workspace_bytes")
+    work = T.empty(need.value // 8, dtype=T.float64, device=dev)  # the first slab is the largest
+    for s, (i0, i1) in enumerate(slabs):
+        ctx.check(ctx.lib.qk_knit_scan(ctx.handle, K, ma, mb, A.data_ptr(), lda, B.data_ptr(), ldb, K2, _ptr(A2), lda2,
+                                       _ptr(B2), ldb2, i0, i1, _SCAN_ENTROPY if entropy else 0, tau,
+                                       stats[s].data_ptr(), counts[s].data_ptr(), _ptr(hists[s]) if hist else None,
+                                       work.data_ptr(), need.value), "qk_knit_scan")
+    st, ct = stats.cpu().numpy(), counts.cpu().numpy()
+    out = {}
+    for slot, name in enumerate(SCAN_STATS):
+        col = st[:, slot]
+        if name in ("max", "maxd"):
+            out[name] = float(col.max())
+        elif name == "min":
+            out[name] = float(col.min())
+        else:
+            acc = np.float64(0.0)
+            for v in col:  # ascending slabs
+                acc = acc + v
+            out[name] = float(acc)
+    out["count_tau"], out["count_pos"] = int(ct[:, 0].sum()), int(ct[:, 1].sum())
+    # the slabs ascend in flat index: the first slab that holds the extreme value holds its lowest index
+    out["argmax"] = int(ct[int(np.argmax(st[:, 5])), 2])
+    out["argmin"] = int(ct[int(np.argmin(st[:, 6])), 3])
+    out["hist"] = hists.sum(0).cpu().numpy() if hist else None
+    return out
+
+
+def knit_collect(ctx: Context, A, B, tau: float, capacity: int):
+    """``qk_knit_collect``: ``(idx, vals, count)`` of the outputs ``R[i][j] > tau`` of the knit of ``A`` and ``B``
+    (as :func:`knit_scan`): device int64 flat indices ``i << mb | j`` and float64 values, in unspecified order,
+    and the Python int ``count`` of such outputs. ``count`` may exceed ``capacity``; the tensors then hold
+    ``capacity`` of the outputs. The values are bit-identical to those the scan sees."""
+    T = torch()
+    K, ma, lda = _scan_side("A", A)
+    _, mb, ldb = _scan_side("B", B, K)
+    if B.device != A.device:
+        raise ValueError("A and B must be on one device")
+    capacity, tau = int(capacity), float(tau)
+    if capacity < 0 or tau != tau:
+        raise ValueError(f"capacity {capacity} must not be negative and tau {tau} must be a number")
+    idx = T.empty(capacity, dtype=T.int64, device=A.device)
+    vals = T.empty(capacity, dtype=T.float64, device=A.device)
+    n_dev = T.zeros(1, dtype=T.int64, device=A.device)
+    used = total = 0
+    for i0, i1 in scan_slabs(ma, mb):
+        room = capacity - used
+        ctx.check(ctx.lib.qk_knit_collect(ctx.handle, K, ma, mb, A.data_ptr(), lda, B.data_ptr(), ldb, i0, i1, tau, room,
+                                          idx[used:].data_ptr() if room else None,
+                                          vals[used:].data_ptr() if room else None, n_dev.data_ptr()), "qk_knit_collect")
+        n = int(n_dev[0])
+        total += n
+        used += min(n, room)
+    return idx[:used], vals[:used], total
+
+
 # ----------------------------------------------------------------------------- shot sampling
 _SEED_STRIDE = 0x632BE59BD9B4E019  # per-fragment stream offset (mirrored by oracle/sampling.py)
 _U64 = (1 << 64) - 1

@@ -36,6 +36,8 @@ up to ``2^(N-k)`` entries, so that bound does not carry over.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 
 from . import engine
@@ -385,6 +387,147 @@ def match_fragments(clbits_a: list, clbits_b: list, kept) -> tuple:
         if s and g not in used:
             raise ValueError(f"the fragments cut the clbits differently: {sorted(s)} on one side only")
     return pairs, [f for f, s in enumerate(seq_a) if not s], [g for g, s in enumerate(seq_b) if not s]
+
+
+# ----------------------------------------------------------------------------- the streamed scan: host models
+SCAN_SIDE_BYTES = 4 << 30  # a side's operand [K, 2^bits] float64 beyond this is refused
+SCAN_BINS = engine.SCAN_BINS
+
+
+def scan_shape(ma: int, mb: int, i_begin: int = 0, i_end: int | None = None, tile: int = 128,
+               max_groups: int = 512) -> dict:
+    """The decomposition ``qk_knit_scan`` / ``qk_knit_collect`` use for a launch (qknit_scan.hip: sc_make_shape):
+    ``tiles_m x tiles_n`` tiles of ``tile x tile`` outputs, tile ``t = (t // tiles_n, t % tiles_n)`` with the tile
+    rows counted from ``i_begin``; ``groups = min(tiles, max_groups)`` workgroups, workgroup ``g`` owning the tiles
+    ``g, g + groups, ...`` (:func:`scan_group_tiles`). A function of ``(mb, i_begin, i_end)`` alone."""
+    i_end = 1 << ma if i_end is None else i_end
+    if not (0 <= ma <= 30 and 0 <= mb <= 30 and 0 <= i_begin < i_end <= 1 << ma):
+        raise ValueError(f"0 <= ma, mb <= 30 and 0 <= i_begin < i_end <= 2^ma, not ({ma}, {mb}, {i_begin}, {i_end})")
+    tiles_m, tiles_n = -(-(i_end - i_begin) // tile), -(-(1 << mb) // tile)
+    tiles = tiles_m * tiles_n
+    groups = min(tiles, max_groups)
+    return dict(tile=tile, i_begin=i_begin, i_end=i_end, n=1 << mb, tiles_m=tiles_m, tiles_n=tiles_n, tiles=tiles,
+                groups=groups, workspace_bytes=groups * 18 * 8)
+
+
+def scan_group_tiles(shape: dict, g: int) -> list:
+    """The tiles of workgroup ``g`` of a :func:`scan_shape`, in the order it walks them: ``(i0, i1, j0, j1)``."""
+    out, T = [], shape["tile"]
+    for t in range(g, shape["tiles"], shape["groups"]):
+        i0, j0 = shape["i_begin"] + (t // shape["tiles_n"]) * T, (t % shape["tiles_n"]) * T
+        out.append((i0, min(i0 + T, shape["i_end"]), j0, min(j0 + T, shape["n"])))
+    return out
+
+
+def scan_sides(widths) -> tuple:
+    """Assign fragments of ``widths[f]`` kept bits to the two sides of the scan: ``(side_a, side_b)``, lists of
+    fragment indices. The widest fragment first (ties: the lower index), onto the side with fewer bits so far,
+    ties to A; a fragment with no kept bit goes to A (it only scales A's rows). A side lists its fragments in the
+    order they were placed: the first occupies the lowest bits of the side's index. One fragment leaves B empty
+    (a column of ones)."""
+    widths = [int(w) for w in widths]
+    if any(w < 0 for w in widths):
+        raise ValueError(f"negative width in {widths}")
+    a, b, na, nb = [], [], 0, 0
+    for f in sorted(range(len(widths)), key=lambda f: (-widths[f], f)):
+        if widths[f] == 0 or na <= nb:
+            a.append(f)
+            na += widths[f]
+        else:
+            b.append(f)
+            nb += widths[f]
+    return a, b
+
+
+def scan_bin(p) -> np.ndarray:
+    """The histogram bin of positive values: ``clamp(-ilogb(p), 0, 127)``."""
+    _, e = np.frexp(np.asarray(p, dtype=np.float64))  # p = f 2^e, 0.5 <= f < 1: ilogb = e - 1
+    return np.clip(1 - e.astype(np.int64), 0, SCAN_BINS - 1)
+
+
+def knit_scan_host(Xs: list, Ys: list | None = None, tau: float = 0.0) -> dict:
+    """numpy model of ``qk_knit_scan`` in ``np.longdouble``, named as :func:`engine.knit_scan` names them. The knit
+    is ``R[x] = sum_k prod_f Xs[f][k, x_f]`` over operands ``[K, 2^m_f]`` with fragment 0 in the lowest bits of the
+    flat index ``x`` (the Khatri-Rao order); ``Ys``: a second knit on the same outputs. ``hist`` counts the float64
+    value of every positive output; ``argmax`` / ``argmin`` are the lowest flat index among equal values."""
+    def flat(Zs):
+        R = np.ones((np.asarray(Zs[0]).shape[0], 1), dtype=np.longdouble)
+        for Z in Zs:  # the new fragment above the bits so far
+            Z = np.asarray(Z, dtype=np.longdouble)
+            R = (Z[:, :, None] * R[:, None, :]).reshape(Z.shape[0], -1)
+        return R.sum(axis=0)
+
+    if not Xs:
+        raise ValueError("no fragment")
+    R = flat(Xs)
+    P = np.maximum(R, 0)
+    pos = R > 0
+    lnP = np.log(P, where=pos, out=np.zeros_like(P))
+    hist = np.bincount(scan_bin(R[pos].astype(np.float64)), minlength=SCAN_BINS).astype(np.int64)
+    out = dict(sum=R.sum(), abs=np.abs(R).sum(), pos=P.sum(), sq=(R * R).sum(), ent=-(P * lnP).sum(), max=R.max(),
+               min=R.min(), sum2=0.0, pos2=0.0, cross=0.0, hell=0.0, l1d=0.0, maxd=0.0,
+               count_tau=int((R > tau).sum()), count_pos=int(pos.sum()), argmax=int(np.argmax(R)),
+               argmin=int(np.argmin(R)), hist=hist, values=R)
+    if Ys is not None:
+        if len(Ys) != len(Xs) or any(np.asarray(X).shape[1] != np.asarray(Y).shape[1] for X, Y in zip(Xs, Ys)):
+            raise ValueError("the two knits have different fragments")
+        R2 = flat(Ys)
+        P2 = np.maximum(R2, 0)
+        out.update(sum2=R2.sum(), pos2=P2.sum(), cross=(R * R2).sum(), hell=np.sqrt(P * P2).sum(),
+                   l1d=np.abs(R - R2).sum(), maxd=np.abs(R - R2).max(), values2=R2)
+    return out
+
+
+def histogram_threshold(hist, k: int) -> tuple:
+    """``(tau, count)`` for the ``k`` largest outputs from a scan's histogram: the smallest bin ``b`` whose
+    cumulative count (bin 0 holds the largest values) reaches ``k``, ``tau`` the largest double below that bin's
+    lower edge ``2^-b`` and ``count`` the number of outputs ``> tau``, known before anything is collected. Bin 127
+    has no lower edge but 0, and ``k`` above the support gives ``(0.0, support)``: every positive output."""
+    hist = np.asarray(hist, dtype=np.int64)
+    if hist.shape != (SCAN_BINS,) or k < 0:
+        raise ValueError(f"a histogram of {SCAN_BINS} bins and k >= 0, not {hist.shape} and {k}")
+    cum = np.cumsum(hist)
+    b = int(np.searchsorted(cum, k, side="left"))
+    if k == 0 or b >= SCAN_BINS - 1:
+        return (np.inf, 0) if k == 0 else (0.0, int(cum[-1]))
+    return float(np.nextafter(np.ldexp(1.0, -b), 0.0)), int(cum[b])
+
+
+def _side_operand(ctx, parts: list, K: int, dev):
+    """One side of the scan from ``parts = [X_f [K, 2^w_f], ...]``: their Khatri-Rao product, the first part in the
+    lowest bits; parts of one column only scale the rows; no part at all is a column of ones."""
+    T = engine.torch()
+    bits = sum(X.shape[1].bit_length() - 1 for X in parts)
+    if bits > 30 or K * 8 << bits > SCAN_SIDE_BYTES:
+        raise ValueError(f"a side of the scan holds K = {K} terms of {bits} bits: [{K}, 2^{bits}] float64 exceeds "
+                         f"SCAN_SIDE_BYTES = {SCAN_SIDE_BYTES}")
+    X = scale = None
+    for Xf in parts:
+        if Xf.shape[1] == 1:
+            scale = Xf if scale is None else scale * Xf
+        else:
+            X = Xf if X is None else engine.khatri_rao(ctx, X.contiguous(), Xf.contiguous())
+    if X is None:
+        X = T.ones((K, 1), dtype=T.float64, device=dev)
+    return X if scale is None else X * scale
+
+
+@dataclass
+class KnitScan:
+    """What :meth:`KnitReducer.scan` returns: statistics of the exact knit (or a marginal of it) ``R``."""
+    mass: float            # sum R
+    l1: float              # sum |R|
+    positive_mass: float   # sum max(R, 0)
+    negativity: float      # (l1 - mass) / 2: the negative mass of the quasi-distribution
+    collision: float       # sum R^2
+    shannon_entropy: float  # bits, of p = max(R, 0) / positive_mass (nan without the entropy term)
+    max: float
+    argmax: int            # key of the maximum, the lowest flat index among equal values
+    min: float
+    argmin: int
+    count_above: int       # outputs with R > threshold (strict)
+    support: int           # outputs with R > 0
+    histogram: np.ndarray  # int64 [128]: positive outputs by binade, bin clamp(-ilogb(p), 0, 127)
 
 
 MOMENT_WORK_BYTES = 256 << 20  # the [rows, K'] temporaries of KnitReducer.overlap: K beyond it goes in row blocks
@@ -833,6 +976,154 @@ class KnitReducer:
         if set(a) & set(b):
             raise ValueError(f"clbits {sorted(set(a) & set(b))} in both lists")
         return self.renyi2_entropy(a) + self.renyi2_entropy(b) - self.renyi2_entropy(a + b)
+
+    # -- nonlinear functionals: the streamed scan ------------------------------------------------
+    def _scan_operands(self, cl: list, other=None) -> tuple:
+        """``(A, B, where_a, where_b, A2, B2)``: the two sides of the scan of the marginal onto ``cl``
+        (:func:`scan_sides` of the fragments' kept widths; a side is the Khatri-Rao product of its fragments'
+        reduced operands) and, per side, the key bit of every bit of its index. ``other``: the same sides of another
+        reducer's knit, its fragments paired by :func:`match_fragments` and permuted to this one's bit order."""
+        T = engine.torch()
+        dev = T.device("cuda", self.device)
+        if not self.frags:
+            mats, where, K = [T.full((1, 1), self._scalar, dtype=T.float64, device=dev)], [[]], 1
+        else:
+            keep, where = key_positions(cl, self.clbits)
+            mats, K = self._operands(keep, [[0]] * len(keep)), self.ops.num_terms
+        sa, sb = scan_sides([len(w) for w in where])
+        A = _side_operand(self.ctx, [mats[f] for f in sa], K, dev)
+        B = _side_operand(self.ctx, [mats[f] for f in sb], K, dev)
+        wa, wb = [b for f in sa for b in where[f]], [b for f in sb for b in where[f]]
+        if other is None:
+            return A, B, wa, wb, None, None
+        pairs, _, only_o = match_fragments(self.clbits if self.frags else [[]], other.clbits if other.frags else [[]], cl)
+        if not other.frags:
+            omats, K2 = [T.full((1, 1), other._scalar, dtype=T.float64, device=dev)], 1
+        else:
+            okeep, _ = key_positions(cl, other.clbits)
+            omats, K2 = other._operands(okeep, [[0]] * len(okeep)), other.ops.num_terms
+        partner = {f: _permute_bits(T, omats[g], order) for f, g, order in pairs}
+        extra = [omats[g] for g in only_o]  # no kept clbit: they scale side A
+        A2 = _side_operand(self.ctx, [partner[f] for f in sa if f in partner] + extra, K2, dev)
+        B2 = _side_operand(self.ctx, [partner[f] for f in sb if f in partner], K2, dev)
+        return A, B, wa, wb, A2, B2
+
+    @staticmethod
+    def _scan_key(flat, mb: int, wa: list, wb: list):
+        """Flat scan indices ``i << mb | j`` (an int or an int64 tensor) as keys."""
+        return deposit_bits(deposit_bits(flat & 0, flat >> mb, wa), flat & ((1 << mb) - 1), wb)
+
+    def _scan_clbits(self, clbits) -> list:
+        return list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+
+    def scan(self, clbits=None, *, threshold: float = 0.0, entropy: bool = True) -> KnitScan:
+        """Statistics of the exact knit ``R`` (``clbits``: of its marginal onto them, bit ``i`` of a key =
+        ``clbits[i]``) that do not factorise over the fragments, without its 2^N output: the knit is formed tile by
+        tile on the matrix cores and consumed in registers (``qk_knit_scan``, DESIGN.md §4a "Nonlinear
+        functionals"). ``threshold``: ``count_above`` counts ``R > threshold``. ``entropy=False`` skips the
+        logarithm (``shannon_entropy`` is then nan). Keys with a bit set on a clbit that no fragment measures hold
+        exact zeros: they are not scanned but enter ``min`` / ``max`` / ``count_above`` as such. Deterministic: two
+        calls return the same values."""
+        self.ctx.bind_stream()
+        cl = self._scan_clbits(clbits)
+        A, B, wa, wb, _, _ = self._scan_operands(cl)
+        st = engine.knit_scan(self.ctx, A, B, tau=threshold, entropy=entropy, hist=True)
+        mb, P = len(wb), st["pos"]
+        H = (st["ent"] / P + np.log(P)) / np.log(2.0) if entropy and P > 0 else float("nan")
+        # key bits that no fragment measures: every key with one of them set holds an exact zero
+        dead = [b for b in range(len(cl)) if b not in wa and b not in wb]
+        if dead:
+            zero_key = 1 << dead[0]  # the lowest such key
+            if threshold < 0:
+                st["count_tau"] += ((1 << len(dead)) - 1) << (len(wa) + len(wb))
+            if st["max"] < 0:
+                st["max"], st["argmax"] = 0.0, None
+            if st["min"] > 0:
+                st["min"], st["argmin"] = 0.0, None
+        key = lambda flat: zero_key if flat is None else int(self._scan_key(flat, mb, wa, wb))
+        return KnitScan(mass=st["sum"], l1=st["abs"], positive_mass=P, negativity=(st["abs"] - st["sum"]) / 2,
+                        collision=st["sq"], shannon_entropy=float(H), max=st["max"],
+                        argmax=key(st["argmax"]), min=st["min"],
+                        argmin=key(st["argmin"]), count_above=st["count_tau"],
+                        support=st["count_pos"], histogram=st["hist"])
+
+    def shannon_entropy(self, clbits=None) -> float:
+        """The Shannon entropy in bits of ``p = max(R_S, 0) / sum max(R_S, 0)`` (:meth:`scan`)."""
+        return self.scan(clbits).shannon_entropy
+
+    def negativity(self, clbits=None) -> float:
+        """The negative mass ``(sum |R_S| - sum R_S) / 2`` of the quasi-distribution (:meth:`scan`)."""
+        return self.scan(clbits, entropy=False).negativity
+
+    def mode(self, clbits=None) -> tuple:
+        """``(key, value)`` of the most probable outcome, the lowest flat index among equal values (:meth:`scan`)."""
+        sc = self.scan(clbits, entropy=False)
+        return sc.argmax, sc.max
+
+    def _collect_sorted(self, A, B, wa: list, wb: list, tau: float, capacity: int):
+        T = engine.torch()
+        idx, vals, count = engine.knit_collect(self.ctx, A, B, tau, capacity)
+        if count > capacity:
+            raise ValueError(f"{count} outcomes above {tau!r}, more than capacity = {capacity}")
+        keys = self._scan_key(idx, len(wb), wa, wb)
+        keys, by_key = T.sort(keys)
+        vals, by_val = T.sort(vals[by_key], descending=True, stable=True)  # ties stay in key order
+        return keys[by_val], vals
+
+    def heavy_outputs(self, threshold: float, clbits=None, capacity: int = 1 << 24) -> tuple:
+        """Device ``(keys int64, values float64)`` of every outcome with ``R_S > threshold`` (strict), sorted by
+        value descending, ties by key ascending (``qk_knit_collect``). ``threshold >= 0``: a key on a clbit that no
+        fragment measures holds a zero and is never listed. ``ValueError``, naming the count, when more than
+        ``capacity`` outcomes qualify."""
+        if not float(threshold) >= 0:
+            raise ValueError(f"threshold must not be negative, not {threshold}")
+        self.ctx.bind_stream()
+        A, B, wa, wb, _, _ = self._scan_operands(self._scan_clbits(clbits))
+        return self._collect_sorted(A, B, wa, wb, float(threshold), int(capacity))
+
+    def top_k(self, k: int, clbits=None, capacity: int = 1 << 24) -> tuple:
+        """Device ``(keys, values)`` of the ``k`` most probable outcomes (fewer when fewer are positive), sorted as
+        :meth:`heavy_outputs`: one scan with the histogram, then :func:`histogram_threshold` gives a threshold whose
+        count is known before anything is collected. ``ValueError``, naming the count, when the binade that holds
+        the ``k``-th value makes that count exceed ``capacity`` (a uniform output, say)."""
+        self.ctx.bind_stream()
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"k must not be negative, not {k}")
+        A, B, wa, wb, _, _ = self._scan_operands(self._scan_clbits(clbits))
+        st = engine.knit_scan(self.ctx, A, B, hist=True)
+        tau, count = histogram_threshold(st["hist"], k)
+        if count > capacity:
+            raise ValueError(f"{count} outcomes share the binades of the top {k}, more than capacity = {capacity}")
+        keys, vals = self._collect_sorted(A, B, wa, wb, tau, count)
+        return keys[:k], vals[:k]
+
+    def _pair_scan(self, other, clbits) -> dict:
+        if not isinstance(other, KnitReducer):
+            raise ValueError("other must be a KnitReducer")
+        if other.N != self.N:
+            raise ValueError(f"{self.N} clbits against {other.N}")
+        if other.device != self.device:
+            raise ValueError(f"reducers on devices {self.device} and {other.device}")
+        self.ctx.bind_stream()
+        A, B, _, _, A2, B2 = self._scan_operands(self._scan_clbits(clbits), other)
+        return engine.knit_scan(self.ctx, A, B, A2, B2)
+
+    def hellinger_fidelity(self, other, clbits=None) -> float:
+        """The Hellinger fidelity ``(sum sqrt(p q))^2 / (sum p sum q)`` of ``p = max(R_S, 0)`` and
+        ``q = max(R'_S, 0)``, the two knits clipped (the normalisation of ``engine.fidelity_from_sums``), without
+        either output: one pair scan. ``other``: a reducer with the same clbits whose fragments cut ``clbits`` as
+        this one's do (:func:`match_fragments`; ``ValueError`` otherwise)."""
+        st = self._pair_scan(other, clbits)
+        return engine.fidelity_from_sums(st["hell"], st["pos"], st["pos2"])
+
+    def total_variation(self, other, clbits=None) -> float:
+        """``sum |R_S - R'_S| / 2`` (one pair scan; arguments as :meth:`hellinger_fidelity`)."""
+        return self._pair_scan(other, clbits)["l1d"] / 2
+
+    def max_difference(self, other, clbits=None) -> float:
+        """``max |R_S - R'_S|`` (one pair scan; arguments as :meth:`hellinger_fidelity`)."""
+        return self._pair_scan(other, clbits)["maxd"]
 
     def marginal_parity(self, clbits, masks):
         """The mixed form: device fp64 ``[M, 2^k]``, row j the marginal onto ``clbits`` of

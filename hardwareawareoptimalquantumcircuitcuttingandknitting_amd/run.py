@@ -639,3 +639,41 @@ def run_virtual_circuit_overlap(virt_a: VirtualCircuit, virt_b: VirtualCircuit, 
     now = perf_counter()
     value = red_a.overlap(red_b, clbits)
     return value, RunTimeInfo(time_a + time_b, perf_counter() - now)
+
+
+def run_virtual_circuit_scan(virt: VirtualCircuit, clbits=None, *, threshold: float = 0.0, device: int = 0,
+                             factored: bool | None = None, group=None, sample: bool = False):
+    """Statistics of the exact knit that do not factorise over the fragments (mass, L1 norm and negativity, Shannon
+    entropy, extrema and their keys, counts, a histogram of binades), of its marginal onto ``clbits`` (``None`` = all
+    clbits), without the 2^N output: the knit is formed tile by tile on the matrix cores and consumed in registers
+    (:meth:`observables.KnitReducer.scan`, ``qk_knit_scan``). Returns ``(observables.KnitScan, RunTimeInfo)``; the
+    sweep is ``run_time``, the scan ``knit_time``. Same restrictions as :func:`run_virtual_circuit_marginal`."""
+    red, run_time = _reducer(virt, device, factored, group, sample)
+    now = perf_counter()
+    value = red.scan(clbits, threshold=threshold)
+    return value, RunTimeInfo(run_time, perf_counter() - now)
+
+
+def run_virtual_circuit_top_k(virt: VirtualCircuit, k: int, clbits=None, *, capacity: int = 1 << 24, device: int = 0,
+                              factored: bool | None = None, group=None, sample: bool = False):
+    """The ``k`` most probable outcomes of the exact knit (of its marginal onto ``clbits``) without the 2^N output
+    (:meth:`observables.KnitReducer.top_k`: a scan with a histogram, then ``qk_knit_collect``). Returns
+    ``({key: value} in descending order of value, RunTimeInfo)``. Same restrictions as
+    :func:`run_virtual_circuit_marginal`."""
+    red, run_time = _reducer(virt, device, factored, group, sample)
+    now = perf_counter()
+    keys, vals = red.top_k(k, clbits, capacity)
+    return dict(zip(keys.tolist(), vals.tolist())), RunTimeInfo(run_time, perf_counter() - now)
+
+
+def run_virtual_circuit_fidelity(virt_a: VirtualCircuit, virt_b: VirtualCircuit, clbits=None, *, device: int = 0,
+                                 factored: bool | None = None, group=None, sample: bool = False):
+    """The Hellinger fidelity of the exact knits of two cut circuits, marginalised onto ``clbits`` (``None`` = all),
+    without either 2^N output (:meth:`observables.KnitReducer.hellinger_fidelity`). The circuits must have the same
+    number of clbits and, on ``clbits``, fragments that measure the same sets. Returns ``(float, RunTimeInfo)``; both
+    sweeps are ``run_time``. Same restrictions as :func:`run_virtual_circuit_marginal`."""
+    red_a, time_a = _reducer(virt_a, device, factored, group, sample)
+    red_b, time_b = _reducer(virt_b, device, factored, group, sample)
+    now = perf_counter()
+    value = red_a.hellinger_fidelity(red_b, clbits)
+    return value, RunTimeInfo(time_a + time_b, perf_counter() - now)

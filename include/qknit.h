@@ -570,6 +570,61 @@ int qk_gram_rows_workspace_bytes(int64_t RA, int64_t RB, int m, int64_t* bytes);
 int qk_gram_rows(qk_ctx* ctx, int64_t RA, int64_t RB, int m, const double* A, int64_t lda, const double* B,
                  int64_t ldb, double* G, int64_t ldg, void* ws, int64_t ws_bytes);
 
+/* ---- nonlinear functionals of the knit (qknit_scan.hip): the streamed scan, no 2^N output ------------------
+ * R[i][j] = sum_{k<K} A[k * lda + i] * B[k * ldb + j] for i in [i_begin, i_end), j < 2^mb is formed in 128 x 128
+ * tiles on the fp64 matrix cores and consumed in registers; the flat index of an output is (i << mb) | j.
+ * 0 <= ma, mb <= 30, K >= 1 (any value), 0 <= i_begin < i_end <= 2^ma, lda >= 2^ma, ldb >= 2^mb (rows at any 8-byte
+ * offset). K2 > 0 adds a second knit R' = A2^T B2 on the same (i, j) (K2 = 0: none, its arguments are ignored).
+ * All buffers but ctx are DEVICE pointers; the operands are only read.
+ *
+ * qk_knit_scan: stats[QK_SCAN_NSTATS] doubles
+ *   SUM = sum R, ABS = sum |R|, POS = sum max(R, 0), SQ = sum R^2, MAX, MIN,
+ *   ENT = sum -p ln p with p = max(R, 0) (0 at p = 0): only with QK_SCAN_ENTROPY in flags, else 0.0,
+ *   with K2 > 0 (else 0.0): SUM2 = sum R', POS2 = sum max(R', 0), CROSS = sum R R',
+ *   HELL = sum sqrt(max(R, 0) max(R', 0)), L1D = sum |R - R'|, MAXD = max |R - R'|;
+ * counts[QK_SCAN_NCOUNTS] int64: COUNT_TAU = #{R > tau} (strict), COUNT_POS = #{R > 0}, ARGMAX / ARGMIN = the
+ * flat index of the maximum / minimum, the lowest index among equal values;
+ * hist (QK_SCAN_BINS int64, or null): an output p > 0 counts in bin clamp(-ilogb(p), 0, 127): bin b in 1..126
+ * holds [2^-b, 2^-(b-1)), bin 0 every p >= 1, bin 127 every 0 < p < 2^-126.
+ * `work`: qk_knit_scan_workspace_bytes(ma, mb, i_begin, i_end) bytes.
+ * Deterministic: no floating-point atomics. The number of workgroups and the tiles of each are a function of
+ * (mb, i_begin, i_end) alone (observables.scan_shape); a thread adds its outputs in ascending tile order, a
+ * workgroup combines its threads by a halving tree, a second kernel adds the workgroups in ascending order.
+ * Two launches give identical bytes; integer data with partial sums below 2^53 is exact.
+ *
+ * qk_knit_collect: appends (flat index, R) of every output with R > tau to idx / vals in unspecified order, one
+ * atomic per wave; *count_dev is the number of such outputs and may exceed `capacity`, in which case only
+ * `capacity` entries are written. The values are bit-identical to those qk_knit_scan saw (the same mainloop). */
+#define QK_SCAN_SUM 0
+#define QK_SCAN_ABS 1
+#define QK_SCAN_POS 2
+#define QK_SCAN_SQ 3
+#define QK_SCAN_ENT 4
+#define QK_SCAN_MAX 5
+#define QK_SCAN_MIN 6
+#define QK_SCAN_SUM2 7
+#define QK_SCAN_POS2 8
+#define QK_SCAN_CROSS 9
+#define QK_SCAN_HELL 10
+#define QK_SCAN_L1D 11
+#define QK_SCAN_MAXD 12
+#define QK_SCAN_NSTATS 16
+#define QK_SCAN_COUNT_TAU 0
+#define QK_SCAN_COUNT_POS 1
+#define QK_SCAN_ARGMAX 2
+#define QK_SCAN_ARGMIN 3
+#define QK_SCAN_NCOUNTS 4
+#define QK_SCAN_BINS 128
+#define QK_SCAN_ENTROPY 1 /* flags */
+int qk_knit_scan_workspace_bytes(int ma, int mb, int64_t i_begin, int64_t i_end, int64_t* bytes);
+int qk_knit_scan(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int64_t lda, const double* B, int64_t ldb,
+                 int64_t K2, const double* A2, int64_t lda2, const double* B2, int64_t ldb2, int64_t i_begin,
+                 int64_t i_end, int flags, double tau, double* stats, int64_t* counts, int64_t* hist, void* work,
+                 int64_t work_bytes);
+int qk_knit_collect(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int64_t lda, const double* B,
+                    int64_t ldb, int64_t i_begin, int64_t i_end, double tau, int64_t capacity, int64_t* idx,
+                    double* vals, int64_t* count_dev);
+
 int qk_hellinger(qk_ctx* ctx, int64_t n, const double* p, const double* q, double* acc3);
 
 #ifdef __cplusplus

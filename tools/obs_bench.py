@@ -25,7 +25,9 @@ route with its one-off cost wins.
 profiles/obs_bench_lookup.json): see lookup_leg.
 
 ``--moments`` runs the second-moments leg instead (``--out``: e.g. profiles/obs_bench_moments.json): see
-moments_leg."""
+moments_leg.
+
+``--scan`` runs the streamed-scan leg instead (``--out``: e.g. profiles/obs_bench_scan.json): see scan_leg."""
 import argparse
 import glob
 import json
@@ -383,8 +385,92 @@ def moments_leg(args):
             fh.write("\n")
 
 
+def scan_leg(args):
+    """Nonlinear functionals (``--out``: e.g. profiles/obs_bench_scan.json) on syc 32 5: (a) qk_knit_scan alone on
+    the prebuilt side operands: plain, with the histogram, with the entropy term, and the pair scan of the knit
+    against itself, each with its achieved TF/s (2 K 2^32 flops per knit formed); (b) KnitReducer.scan from the
+    swept rows, with and without the entropy term, and top_k(16); (c) sweep + scan; (d) the route they replace, in
+    the same process: the dense step plus the same statistics by torch over its 2^32 output."""
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine, observables as ob
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.run import run_virtual_circuit_dense
+
+    res = {"config": "syc_32_5_p2", "device": torch.cuda.get_device_name(0), "reps": 20}
+    _, cut, _ = cutting.config_cut_circuit("syc", 32, 5, 2)
+    virt = VirtualCircuit(cut)
+    red = KnitReducer(virt)
+    ctx = engine.get_context(0)
+    res["fragments"] = [{"rows": int(q.shape[0]), "m": len(cl)} for q, cl in zip(red.qs, red.clbits)]
+    K = res["terms"] = int(red.ops.num_terms)
+    A, B, wa, wb, _, _ = red._scan_operands(list(range(red.N)))
+    res["sides"] = {"bits_a": len(wa), "bits_b": len(wb)}
+    flops = 2.0 * K * 2.0 ** (len(wa) + len(wb))
+    for name, knits, fn in (("plain", 1, lambda: engine.knit_scan(ctx, A, B)),
+                            ("hist", 1, lambda: engine.knit_scan(ctx, A, B, hist=True)),
+                            ("entropy", 1, lambda: engine.knit_scan(ctx, A, B, entropy=True)),
+                            ("entropy_hist", 1, lambda: engine.knit_scan(ctx, A, B, entropy=True, hist=True)),
+                            ("pair_with_itself", 2, lambda: engine.knit_scan(ctx, A, B, A, B))):
+        t = timed(torch, fn)
+        t["TFLOPs"] = knits * flops / t["median_ms"] / 1e9
+        res[f"qk_knit_scan_{name}"] = t
+        print(name, t, flush=True)
+    res["scan_no_entropy"] = timed(torch, lambda: red.scan(entropy=False))
+    print("scan_no_entropy", res["scan_no_entropy"], flush=True)
+    res["scan_entropy"] = timed(torch, lambda: red.scan())
+    res["pair_scan_with_itself"] = timed(torch, lambda: red.hellinger_fidelity(red))
+    # depth 5 is far from Porter-Thomas: millions of outcomes share the binade of the 16th largest value, more
+    # than the default capacity of 2^24
+    tau, count = ob.histogram_threshold(red.scan(entropy=False).histogram, 16)
+    res["top_k_16_collected"] = count
+    res["top_k_16"] = timed(torch, lambda: red.top_k(16, capacity=count))
+    res["sweep_plus_scan_no_entropy"] = timed(torch, lambda: KnitReducer(virt).scan(entropy=False))
+    sc = red.scan()
+    res["values"] = {"mass": sc.mass, "l1": sc.l1, "negativity": sc.negativity, "collision": sc.collision,
+                     "shannon_entropy_bits": sc.shannon_entropy, "max": sc.max, "argmax": sc.argmax, "min": sc.min,
+                     "support": sc.support, "top_16": [float(v) for v in red.top_k(16, capacity=count)[1].tolist()]}
+    if not args.no_dense:
+        del A, B
+        torch.cuda.empty_cache()
+
+        def dense_stats(entropy):
+            full, _ = run_virtual_circuit_dense(virt)
+            p = full.clamp(min=0.0)
+            out = [full.sum(), full.abs().sum(), p.sum(), (full * full).sum(), full.max(), full.argmax(), full.min(),
+                   full.argmin(), (full > 0).sum()]
+            if entropy:
+                out.append(-torch.special.xlogy(p, p).sum())
+            return [float(v) for v in out]
+
+        def dense_top():
+            full, _ = run_virtual_circuit_dense(virt)  # torch.topk takes at most 2^31 - 1 elements: 64 rows first
+            vals, at = torch.topk(full.view(64, -1), 16, dim=1)
+            best, pick = torch.topk(vals.reshape(-1), 16)
+            return best, (pick // 16) * (full.numel() // 64) + at.reshape(-1)[pick]
+
+        vals = dense_stats(True)
+        res["check"] = {"top_16_max_abs_diff": float((dense_top()[0].cpu() - torch.tensor(res["values"]["top_16"])).abs().max()),
+                        "mass_abs_diff": abs(vals[0] - sc.mass), "collision_abs_diff": abs(vals[3] - sc.collision),
+                        "max_abs_diff": abs(vals[4] - sc.max), "argmax_equal": int(vals[5]) == sc.argmax,
+                        "support_diff": int(vals[8]) - sc.support}
+        res["dense_step_only"] = timed(torch, lambda: run_virtual_circuit_dense(virt))
+        res["dense_step_stats_no_entropy"] = timed(torch, lambda: dense_stats(False))
+        res["dense_step_stats_entropy"] = timed(torch, lambda: dense_stats(True))
+        res["dense_step_topk_16"] = timed(torch, dense_top)
+        res["scan_over_dense_no_entropy"] = (res["sweep_plus_scan_no_entropy"]["median_ms"]
+                                             / res["dense_step_stats_no_entropy"]["median_ms"])
+    print(json.dumps(res, indent=1), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scan", action="store_true", help="the streamed-scan leg only (see scan_leg)")
     ap.add_argument("--moments", action="store_true", help="the second-moments leg only (see moments_leg)")
     ap.add_argument("--lookup", action="store_true", help="the probabilities-at-chosen-keys leg only (see lookup_leg)")
     ap.add_argument("--spectrum", action="store_true", help="the Walsh-Hadamard spectrum leg only (see spectrum_leg)")
@@ -403,6 +489,8 @@ def main():
         return lookup_leg(args)
     if args.moments:
         return moments_leg(args)
+    if args.scan:
+        return scan_leg(args)
     import torch
 
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
