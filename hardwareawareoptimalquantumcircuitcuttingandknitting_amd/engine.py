@@ -692,13 +692,9 @@ def reduce_bits(ctx: Context, src, m: int, keep_mask: int, flips, out=None):
     return out
 
 
-def wht_rows(ctx: Context, src, m: int | None = None, out=None):
-    """``qk_wht_rows``: ``out[r, z] = sum over x < 2^m of (-1)^popcount(x & z) * src[r, x]``, the
-    unnormalised Walsh-Hadamard transform of every row -> ``[rows, 2^m]``. ``src``: float64
-    ``[rows, >= 2^m]`` with unit column stride; ``m`` defaults to its column count, which must then be a
-    power of two. ``out`` (optional): a float64 tensor with unit column stride and at least ``2^m``
-    columns (further ones stay as they are); ``out is src`` transforms in place; any other overlap with
-    ``src`` is refused."""
+def _row_transform_args(src, m, out):
+    """The argument checks :func:`wht_rows` and :func:`kron2_rows` share: ``(rows, m, ld_src, out, ld_dst)``, with
+    ``out`` allocated ``[rows, 2^m]`` if it was None. ``ValueError`` before any launch."""
     T = torch()
     if src.dim() != 2 or src.dtype != T.float64 or (src.shape[1] > 1 and src.stride(1) != 1):
         raise ValueError("src must be float64 [rows, >= 2^m] with unit column stride")
@@ -723,14 +719,43 @@ def wht_rows(ctx: Context, src, m: int | None = None, out=None):
     ld_dst = out.stride(0) if rows > 1 else max(out.stride(0), n)
     if ld_src < n or ld_dst < n:
         raise ValueError(f"row stride below 2^m = {n}")
-    if rows == 0:
-        return out
-    if not (src.data_ptr() == out.data_ptr() and ld_src == ld_dst):
+    if rows and not (src.data_ptr() == out.data_ptr() and ld_src == ld_dst):
         s0, d0 = src.data_ptr(), out.data_ptr()
         s1, d1 = s0 + ((rows - 1) * ld_src + n) * 8, d0 + ((rows - 1) * ld_dst + n) * 8
         if s0 < d1 and d0 < s1:
             raise ValueError("src and out overlap: only out = src (same rows, same stride) transforms in place")
+    return rows, m, ld_src, out, ld_dst
+
+
+def wht_rows(ctx: Context, src, m: int | None = None, out=None):
+    """``qk_wht_rows``: ``out[r, z] = sum over x < 2^m of (-1)^popcount(x & z) * src[r, x]``, the
+    unnormalised Walsh-Hadamard transform of every row -> ``[rows, 2^m]``. ``src``: float64
+    ``[rows, >= 2^m]`` with unit column stride; ``m`` defaults to its column count, which must then be a
+    power of two. ``out`` (optional): a float64 tensor with unit column stride and at least ``2^m``
+    columns (further ones stay as they are); ``out is src`` transforms in place; any other overlap with
+    ``src`` is refused."""
+    rows, m, ld_src, out, ld_dst = _row_transform_args(src, m, out)
+    if rows == 0:
+        return out
     ctx.check(ctx.lib.qk_wht_rows(ctx.handle, rows, m, src.data_ptr(), ld_src, out.data_ptr(), ld_dst), "qk_wht_rows")
+    return out
+
+
+def kron2_rows(ctx: Context, src, mats, m: int | None = None, out=None):
+    """``qk_kron2_rows``: ``out[r, y] = sum over x < 2^m of prod_b mats[b][y_b][x_b] * src[r, x]``, one real 2x2
+    matrix per index bit applied to every row -> ``[rows, 2^m]``. ``mats``: ``[m, 2, 2]`` finite values on the
+    host, ``mats[b]`` the matrix of bit ``b``. ``src``, ``m`` and ``out`` as for :func:`wht_rows`, in place
+    included."""
+    rows, m, ld_src, out, ld_dst = _row_transform_args(src, m, out)
+    coef = np.ascontiguousarray(mats, dtype=np.float64)
+    if coef.shape != (m, 2, 2) and not (m == 0 and coef.size == 0):
+        raise ValueError(f"mats must have shape [{m}, 2, 2], not {list(coef.shape)}")
+    if not np.isfinite(coef).all():
+        raise ValueError("mats must be finite")
+    if rows == 0:
+        return out
+    ctx.check(ctx.lib.qk_kron2_rows(ctx.handle, rows, m, coef.ctypes.data_as(ctypes.c_void_p), src.data_ptr(), ld_src,
+                                    out.data_ptr(), ld_dst), "qk_kron2_rows")
     return out
 
 

@@ -29,6 +29,12 @@ Second moments factorise too: ``sum_x R[x] R'[x] = sum_{k,k'} prod_f (X_f X'_f^T
 (``qk_gram_rows``, csrc/qknit_moments.hip): :meth:`KnitReducer.overlap`, ``collision_probability``,
 ``renyi2_entropy``, ``ideal_xeb``, ``l2_distance``, ``mutual_information2``.
 
+A linear map that factorises over the clbits, ``R'[y] = sum_x prod_c A_c[y_c][x_c] R[x]`` with a real 2x2 matrix
+per clbit (readout error, its inverse, a flip, a bit summed out), acts on the column index of each fragment's
+swept rows and commutes with ``W_f``: :meth:`KnitReducer.with_channels` applies it to the rows once
+(``qk_kron2_rows``, csrc/qknit_kron.hip) and returns a reducer whose every answer is that of ``R'``
+(``with_readout_error``, ``with_readout_mitigation``).
+
 It builds on the direct path (``engine.prepare_fragments`` / ``sweep_fragment`` / ``knit_operands``
 / ``fragment_operands`` / ``contract``, as ``run._direct_dense``), not on the cached
 ``KnitPipeline``: the pipeline's row pruning rests on a per-entry bound on ``R`` and a marginal sums
@@ -242,6 +248,93 @@ def wht_host(src, m: int) -> np.ndarray:
         y[..., 0, :] += y[..., 1, :]
         np.subtract(a, y[..., 1, :], out=y[..., 1, :])
     return x
+
+
+def kron2_host(src, m: int, mats) -> np.ndarray:
+    """numpy model of ``qk_kron2_rows``: ``out[..., y] = sum_{x < 2^m} prod_b mats[b][y_b][x_b] src[..., x]``, by
+    ``m`` levels of butterflies ``(a, b) -> (A[0][0] a + A[0][1] b, A[1][0] a + A[1][1] b)`` with ``a`` the element
+    whose bit is clear and ``A = mats[b]``, lowest bit first, in the common dtype of ``src`` and ``mats`` (int64,
+    float64 or ``np.longdouble``; the kernel takes the bits in another fixed order and fuses one product: equal
+    for exactly representable sums, equal to rounding otherwise)."""
+    src, A = np.asarray(src), np.asarray(mats)
+    n = 1 << m
+    if src.shape[-1] < n:
+        raise ValueError(f"{src.shape[-1]} columns for m = {m}")
+    if A.shape != (m, 2, 2) and not (m == 0 and A.size == 0):
+        raise ValueError(f"mats must have shape [{m}, 2, 2], not {list(A.shape)}")
+    x = np.array(src[..., :n], dtype=np.result_type(src.dtype, A.dtype) if m else src.dtype, copy=True, order="C")
+    lead = x.shape[:-1]
+    for b in range(m):
+        y = x.reshape(*lead, n >> (b + 1), 2, 1 << b)
+        lo, hi = y[..., 0, :].copy(), y[..., 1, :].copy()
+        y[..., 0, :] = A[b, 0, 0] * lo + A[b, 0, 1] * hi
+        y[..., 1, :] = A[b, 1, 0] * lo + A[b, 1, 1] * hi
+    return x
+
+
+def readout_matrix(e0: float, e1: float) -> np.ndarray:
+    """The confusion matrix ``[[1 - e0, e1], [e0, 1 - e1]]`` of one clbit: ``A[y][x]`` is the probability of
+    reading ``y`` when the bit is ``x``, ``e0 = P(read 1 | 0)`` and ``e1 = P(read 0 | 1)``, both in [0, 1]."""
+    e0, e1 = float(e0), float(e1)
+    if not (0.0 <= e0 <= 1.0 and 0.0 <= e1 <= 1.0):
+        raise ValueError(f"e0 and e1 must lie in [0, 1], not {e0} and {e1}")
+    return np.array([[1.0 - e0, e1], [e0, 1.0 - e1]])
+
+
+def invert_channels(mats) -> np.ndarray:
+    """The inverse of every 2x2 matrix of ``mats [..., 2, 2]``; ``ValueError`` where a determinant is 0 or not
+    finite."""
+    A = np.asarray(mats, dtype=np.float64)
+    if A.ndim < 2 or A.shape[-2:] != (2, 2):
+        raise ValueError(f"2x2 matrices, not an array of shape {list(A.shape)}")
+    det = A[..., 0, 0] * A[..., 1, 1] - A[..., 0, 1] * A[..., 1, 0]
+    if not np.isfinite(det).all() or (det == 0).any():
+        raise ValueError("a matrix with determinant 0 (or a determinant that is not finite) has no inverse")
+    inv = np.empty_like(A)
+    inv[..., 0, 0], inv[..., 0, 1] = A[..., 1, 1] / det, -A[..., 0, 1] / det
+    inv[..., 1, 0], inv[..., 1, 1] = -A[..., 1, 0] / det, A[..., 0, 0] / det
+    return inv
+
+
+def bit_channels(spec, n_clbits: int, measured) -> np.ndarray:
+    """Per-clbit 2x2 matrices as float64 ``[n_clbits, 2, 2]``. ``spec``: such an array; a dict ``{clbit: 2x2}``,
+    the identity for every other clbit; or one 2x2 matrix for every clbit in ``measured`` (the clbits some
+    fragment measures). A clbit outside ``measured`` reads 0 in every key and can only carry the identity:
+    ``ValueError`` for any other matrix on it, for a clbit out of range, a wrong shape or a value that is not
+    finite."""
+    measured = {int(c) for c in measured}
+    out = np.tile(np.eye(2), (n_clbits, 1, 1))
+    if isinstance(spec, dict):
+        for c, A in spec.items():
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < n_clbits:
+                raise ValueError(f"clbit {c!r} outside 0..{n_clbits - 1}")
+            A = np.asarray(A, dtype=np.float64)
+            if A.shape != (2, 2):
+                raise ValueError(f"clbit {c}: a 2x2 matrix, not shape {list(A.shape)}")
+            out[int(c)] = A
+    else:
+        A = np.asarray(spec, dtype=np.float64)
+        if A.shape == (2, 2):
+            out[sorted(measured)] = A
+        elif A.shape == (n_clbits, 2, 2):
+            out[:] = A
+        else:
+            raise ValueError(f"channels must be [{n_clbits}, 2, 2], a dict {{clbit: 2x2}} or one 2x2 matrix, "
+                             f"not shape {list(A.shape)}")
+    if not np.isfinite(out).all():
+        raise ValueError("channel matrices must be finite")
+    for c in range(n_clbits):
+        if c not in measured and not np.array_equal(out[c], np.eye(2)):
+            raise ValueError(f"no fragment measures clbit {c}: it is always 0 and takes only the identity")
+    return out
+
+
+def check_stochastic(mats, tol: float = 1e-12) -> None:
+    """``ValueError`` unless every matrix of ``mats [..., 2, 2]`` is column-stochastic: no negative entry and
+    column sums within ``tol`` of 1."""
+    A = np.asarray(mats, dtype=np.float64)
+    if (A < 0).any() or (np.abs(A.sum(axis=-2) - 1.0) > tol).any():
+        raise ValueError("a confusion matrix must be column-stochastic: entries >= 0, columns summing to 1")
 
 
 def key_positions(clbits: list, fragment_clbits: list) -> tuple:
@@ -653,6 +746,44 @@ class KnitReducer:
             out[0] = self._scalar
             return out
         return engine.contract(self.ctx, mats, positions, out)
+
+    # -- per-clbit channels ---------------------------------------------------------------------
+    def _measured(self) -> set:
+        return {c for fcl in self.clbits for c in fcl}
+
+    def with_channels(self, spec) -> "KnitReducer":
+        """A reducer of ``R'[y] = sum_x prod_c A_c[y_c][x_c] R[x]``, ``A_c`` the real 2x2 matrix of clbit ``c``
+        (``spec``: see :func:`bit_channels`), without another sweep: the map acts on the column index of each
+        fragment's swept rows, one bit at a time, and commutes with the transform ``W_f`` on their row index, so
+        the new reducer holds the rows transformed out of place (``qk_kron2_rows``; fragment f takes the matrices
+        of its clbits) and shares the context, the fragments and the operands' description with this one. Every
+        answer of the new reducer is that of ``R'``; its caches start empty, and this reducer is left as it is.
+        No fragment at all: the reducer itself (no clbit is measured, only the identity applies)."""
+        mats = bit_channels(spec, self.N, self._measured())
+        if not self.frags:
+            return self
+        self.ctx.bind_stream()
+        new = object.__new__(KnitReducer)
+        new.__dict__.update(self.__dict__)
+        new.qs = [engine.kron2_rows(self.ctx, q, mats[fcl] if fcl else np.zeros((0, 2, 2)), len(fcl))
+                  for q, fcl in zip(self.qs, self.clbits)]
+        new._spectrum = new._transposed = new._moment_specs = new._spectrum_t = None
+        return new
+
+    def with_readout_error(self, confusion) -> "KnitReducer":
+        """:meth:`with_channels` of per-clbit confusion matrices (:func:`readout_matrix`): the distribution a
+        device with that readout error returns. Every matrix must be column-stochastic (:func:`check_stochastic`)."""
+        mats = bit_channels(confusion, self.N, self._measured())
+        check_stochastic(mats)
+        return self.with_channels(mats)
+
+    def with_readout_mitigation(self, confusion) -> "KnitReducer":
+        """:meth:`with_channels` of the inverses of per-clbit confusion matrices (:func:`invert_channels`): the
+        quasi-distribution that readout mitigation makes of this knit. ``confusion`` as for
+        :meth:`with_readout_error`, and every matrix invertible."""
+        mats = bit_channels(confusion, self.N, self._measured())
+        check_stochastic(mats)
+        return self.with_channels(invert_channels(mats))
 
     # -- public ---------------------------------------------------------------------------------
     def marginal(self, clbits):

@@ -494,8 +494,11 @@ def run_virtual_circuit(virt: VirtualCircuit, shots: int = 20000, *, device: int
 
 
 # ---------------------------------------------------------------------------- reductions of the knit
-def _reducer(virt: VirtualCircuit, device: int, factored, group, sample: bool):
-    """Sweep for the marginal / expectation entry points: ``(KnitReducer, run_time)``."""
+def _reducer(virt: VirtualCircuit, device: int, factored, group, sample: bool, *, readout=None, mitigate: bool = False):
+    """Sweep for the marginal / expectation entry points: ``(KnitReducer, run_time)``. ``readout``: per-clbit
+    confusion matrices (``observables.bit_channels``): the reducer then answers for the knit under that readout
+    error (``KnitReducer.with_readout_error``) or, with ``mitigate``, under its inverse
+    (``with_readout_mitigation``); the transform of the swept rows counts into ``run_time``."""
     from .observables import KnitReducer
 
     if group is not None:
@@ -504,16 +507,21 @@ def _reducer(virt: VirtualCircuit, device: int, factored, group, sample: bool):
         raise ValueError("marginals and expectation values are of the exact knit (sample=True is not supported)")
     if not all(isinstance(virt.get_backend(f), MI355XBackend) for f in virt.fragment_circuits if len(f)):
         raise ValueError("marginals and expectation values need every fragment on the MI355X backend")
+    if mitigate and readout is None:
+        raise ValueError("mitigate=True needs the confusion matrices (readout)")
     log.info("Running virtualizer with %d %s fragments and %d vgates...", len(virt.fragment_circuits),
              tuple(len(f) for f in virt.fragment_circuits), len(virt.vgate_instructions))
     now = perf_counter()
     red = KnitReducer(virt, device=device, factored=factored)
+    if readout is not None:
+        red = red.with_readout_mitigation(readout) if mitigate else red.with_readout_error(readout)
     _sync(device)
     return red, perf_counter() - now
 
 
 def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 0, dense: bool = False,
-                                 factored: bool | None = None, group=None, sample: bool = False):
+                                 factored: bool | None = None, group=None, sample: bool = False,
+                                 readout=None, mitigate: bool = False):
     """The knit's distribution of the clbits ``clbits`` alone (bit ``i`` of a key = ``clbits[i]``), all
     others summed out, without the 2^N output: the swept rows are reduced per fragment
     (``qk_reduce_bits``) and knitted narrow (:class:`observables.KnitReducer`). Returns
@@ -524,8 +532,14 @@ def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 
     shape of :func:`run_virtual_circuit`'s result. Note that the projection does not commute with
     summing: the NPD of a marginal is not the marginal of the NPD of the full distribution.
 
+    ``readout``: per-clbit confusion matrices (an ``[N, 2, 2]`` array, a dict ``{clbit: 2x2}`` or one 2x2 matrix for
+    every measured clbit; ``observables.readout_matrix``): the answer is then that of the knit under this readout
+    error, or with ``mitigate=True`` under its inverse, the readout-mitigated quasi-distribution
+    (``KnitReducer.with_readout_error`` / ``with_readout_mitigation``; the swept rows are transformed once, inside
+    ``run_time``). The other single-circuit entry points below take the same two keywords.
+
     One GPU, exact instances, every fragment on the MI355X backend (``ValueError`` otherwise)."""
-    red, run_time = _reducer(virt, device, factored, group, sample)
+    red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
     out = red.marginal(clbits)
     if dense:
@@ -539,7 +553,7 @@ def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 
 
 def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device: int = 0,
                                     factored: bool | None = None, group=None, sample: bool = False,
-                                    weights=None, method: str = "reduce"):
+                                    weights=None, method: str = "reduce", readout=None, mitigate: bool = False):
     """Expectation values of Pauli-Z strings on the exact knit (the quasi-distribution itself, no
     projection): ``sum_key (-1)^popcount(key & mask) R[key]`` per observable, without the 2^N output.
     ``observables``: int masks over the clbits, or ``'ZIIZ'`` strings (rightmost character = clbit 0,
@@ -554,7 +568,7 @@ def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device
     by the spectrum route."""
     if method not in ("reduce", "spectrum", "fused"):
         raise ValueError(f"method must be 'reduce', 'spectrum' or 'fused', not {method!r}")
-    red, run_time = _reducer(virt, device, factored, group, sample)
+    red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
     vals = red.expectation(observables, method=method) if weights is None else red.expectation_sum(observables, weights)
     info = RunTimeInfo(run_time, perf_counter() - now)
@@ -564,7 +578,7 @@ def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device
 
 def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed: int = 0, clbits=None,
                               memory: bool = False, device: int = 0, factored: bool | None = None, group=None,
-                              sample: bool = False):
+                              sample: bool = False, readout=None, mitigate: bool = False):
     """``shots`` measurement outcomes distributed as the exact knit, i.e. as the uncut circuit's output,
     without the 2^N distribution: drawn fragment by fragment from the swept rows
     (:meth:`observables.KnitReducer.sample`, ``qk_sample_rows``). Not ``run_virtual_circuit(sample=True)``,
@@ -575,7 +589,7 @@ def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed:
     ``[shots]`` of keys in draw order. ``clbits``: the measured clbits (bit ``i`` of a key = ``clbits[i]``),
     ``None`` = all. A pure function of (circuit, ``seed``, ``shots``); the first ``n`` shots of a longer
     run are an ``n``-shot run. Same restrictions as :func:`run_virtual_circuit_marginal`."""
-    red, run_time = _reducer(virt, device, factored, group, sample)
+    red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
     keys = red.sample(shots, seed, clbits)
     if memory:
@@ -588,7 +602,8 @@ def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed:
 
 
 def run_virtual_circuit_probabilities(virt: VirtualCircuit, keys, *, clbits=None, device: int = 0,
-                                      factored: bool | None = None, group=None, sample: bool = False):
+                                      factored: bool | None = None, group=None, sample: bool = False,
+                                      readout=None, mitigate: bool = False):
     """The exact knit at the given outcome keys, i.e. the probabilities of chosen bitstrings (the
     quasi-distribution itself, no projection), without the 2^N output: one gathered row per fragment and key
     (:meth:`observables.KnitReducer.probabilities`, ``qk_knit_at``). ``keys``: ints, a list, an integer numpy
@@ -596,32 +611,33 @@ def run_virtual_circuit_probabilities(virt: VirtualCircuit, keys, *, clbits=None
     keys are over (bit ``i`` of a key = ``clbits[i]``), ``None`` = all. Returns ``(float64 numpy [M],
     RunTimeInfo)``; the sweep is ``run_time``, the lookup ``knit_time``. Same restrictions as
     :func:`run_virtual_circuit_marginal`."""
-    red, run_time = _reducer(virt, device, factored, group, sample)
+    red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
     vals = red.probabilities(keys, clbits).cpu().numpy()
     return vals, RunTimeInfo(run_time, perf_counter() - now)
 
 
 def run_virtual_circuit_xeb(virt: VirtualCircuit, keys, *, clbits=None, device: int = 0,
-                            factored: bool | None = None, group=None, sample: bool = False):
+                            factored: bool | None = None, group=None, sample: bool = False,
+                            readout=None, mitigate: bool = False):
     """Linear cross-entropy benchmarking score of sampled ``keys`` against the exact knit:
     ``2^k * mean_j R[key_j] - 1`` over the ``k`` measured clbits (:meth:`observables.KnitReducer.linear_xeb`).
     Returns ``(float, RunTimeInfo)``; arguments, timing and restrictions as
     :func:`run_virtual_circuit_probabilities`."""
-    red, run_time = _reducer(virt, device, factored, group, sample)
+    red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
     score = red.linear_xeb(keys, clbits)
     return score, RunTimeInfo(run_time, perf_counter() - now)
 
 
 def run_virtual_circuit_collision(virt: VirtualCircuit, clbits=None, *, device: int = 0, factored: bool | None = None,
-                                  group=None, sample: bool = False):
+                                  group=None, sample: bool = False, readout=None, mitigate: bool = False):
     """The collision probability ``sum_y R_S[y]^2`` of the exact knit's marginal onto ``clbits`` (``None`` =
     all clbits), without the 2^N output: per fragment the Gram matrix of its swept rows (``qk_gram_rows``),
     then sums over pairs of terms (:meth:`observables.KnitReducer.collision_probability`). Returns
     ``(float, RunTimeInfo)``; the sweep is ``run_time``, Grams + combine ``knit_time``. Same restrictions as
     :func:`run_virtual_circuit_marginal`."""
-    red, run_time = _reducer(virt, device, factored, group, sample)
+    red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
     value = red.collision_probability(clbits)
     return value, RunTimeInfo(run_time, perf_counter() - now)
@@ -642,25 +658,27 @@ def run_virtual_circuit_overlap(virt_a: VirtualCircuit, virt_b: VirtualCircuit, 
 
 
 def run_virtual_circuit_scan(virt: VirtualCircuit, clbits=None, *, threshold: float = 0.0, device: int = 0,
-                             factored: bool | None = None, group=None, sample: bool = False):
+                             factored: bool | None = None, group=None, sample: bool = False,
+                             readout=None, mitigate: bool = False):
     """Statistics of the exact knit that do not factorise over the fragments (mass, L1 norm and negativity, Shannon
     entropy, extrema and their keys, counts, a histogram of binades), of its marginal onto ``clbits`` (``None`` = all
     clbits), without the 2^N output: the knit is formed tile by tile on the matrix cores and consumed in registers
     (:meth:`observables.KnitReducer.scan`, ``qk_knit_scan``). Returns ``(observables.KnitScan, RunTimeInfo)``; the
     sweep is ``run_time``, the scan ``knit_time``. Same restrictions as :func:`run_virtual_circuit_marginal`."""
-    red, run_time = _reducer(virt, device, factored, group, sample)
+    red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
     value = red.scan(clbits, threshold=threshold)
     return value, RunTimeInfo(run_time, perf_counter() - now)
 
 
 def run_virtual_circuit_top_k(virt: VirtualCircuit, k: int, clbits=None, *, capacity: int = 1 << 24, device: int = 0,
-                              factored: bool | None = None, group=None, sample: bool = False):
+                              factored: bool | None = None, group=None, sample: bool = False,
+                              readout=None, mitigate: bool = False):
     """The ``k`` most probable outcomes of the exact knit (of its marginal onto ``clbits``) without the 2^N output
     (:meth:`observables.KnitReducer.top_k`: a scan with a histogram, then ``qk_knit_collect``). Returns
     ``({key: value} in descending order of value, RunTimeInfo)``. Same restrictions as
     :func:`run_virtual_circuit_marginal`."""
-    red, run_time = _reducer(virt, device, factored, group, sample)
+    red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
     keys, vals = red.top_k(k, clbits, capacity)
     return dict(zip(keys.tolist(), vals.tolist())), RunTimeInfo(run_time, perf_counter() - now)

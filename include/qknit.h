@@ -515,6 +515,22 @@ int qk_reduce_bits(qk_ctx* ctx, int64_t rows, int m, const double* src, int64_t 
  * the in-place and out-of-place forms agree bit for bit. */
 int qk_wht_rows(qk_ctx* ctx, int64_t rows, int m, const double* src, int64_t ld_src, double* dst, int64_t ld_dst);
 
+/* ---- a 2x2 matrix per outcome bit on every row (qknit_kron.hip): per-clbit channels, e.g. readout error ---
+ * dst[r * ld_dst + y] = sum over x in [0, 2^m) of prod_{b < m} coef[b][2 * y_b + x_b] * src[r * ld_src + x]
+ * for r < rows, y < 2^m: the Kronecker product of m real 2x2 matrices applied to every row, coef[b] =
+ * {A_b[0][0], A_b[0][1], A_b[1][0], A_b[1][1]} being the matrix of index bit b (qk_wht_rows is the case
+ * {1, 1, 1, -1} on every bit). coef is a HOST array of 4 * m finite doubles, read before the call returns
+ * (it travels in the kernel arguments); src / dst are DEVICE pointers. 0 <= m <= 30; ld_src, ld_dst >= 2^m
+ * (columns of dst at and beyond 2^m are not written); src == dst with ld_src == ld_dst transforms in place,
+ * any other overlap of the two row ranges is refused; rows == 0 is a no-op. No workspace; the passes of
+ * qk_wht_rows, of which one whose bits all carry the identity matrix is not launched (out of place the
+ * first pass still copies). Deterministic: no atomics, every output the root of a radix-2 tree fixed by m
+ * and the set of non-identity bits alone, every butterfly output fma(c_own, own, c_other * other); a
+ * row's result does not depend on the other rows, and the in-place and out-of-place forms agree bit for
+ * bit. An output lies within gamma_{2m} of the same sum taken with |coef| and |src|. */
+int qk_kron2_rows(qk_ctx* ctx, int64_t rows, int m, const double* coef, const double* src, int64_t ld_src,
+                  double* dst, int64_t ld_dst);
+
 /* ---- draws from rows of a product that is never stored (qknit_shots.hip): shots from the knit ---
  * u[i] = u(seed, label, first + i) for i < n: the counter-based stream of qk_sample_counts (DEVICE u). */
 int qk_uniforms(qk_ctx* ctx, uint64_t seed, int64_t label, int64_t first, int64_t n, double* u);

@@ -27,7 +27,10 @@ profiles/obs_bench_lookup.json): see lookup_leg.
 ``--moments`` runs the second-moments leg instead (``--out``: e.g. profiles/obs_bench_moments.json): see
 moments_leg.
 
-``--scan`` runs the streamed-scan leg instead (``--out``: e.g. profiles/obs_bench_scan.json): see scan_leg."""
+``--scan`` runs the streamed-scan leg instead (``--out``: e.g. profiles/obs_bench_scan.json): see scan_leg.
+
+``--channels`` runs the per-clbit channels leg instead (``--out``: e.g. profiles/obs_bench_channels.json): see
+channels_leg."""
 import argparse
 import glob
 import json
@@ -468,8 +471,96 @@ def scan_leg(args):
             fh.write("\n")
 
 
+def channels_leg(args):
+    """Per-clbit channels (``--out``: e.g. profiles/obs_bench_channels.json): on [64, 2^16] and [256, 2^16], the
+    fragment shapes of syc 32 5, (a) qk_kron2_rows with 16 non-identity bits, out of place and in place, with its
+    achieved bytes/s (two passes, each reading and writing every element) and flop/s (a product and a fused
+    multiply-add per element and bit); (b) qk_wht_rows on the same buffers in the same process; (c) the torch route
+    on the same source: a ``[rows * 2^(15 - b), 2, 2^b]`` view and one einsum per bit. A single call is two short
+    launches, so (a)-(c) are also timed as 50 calls between one pair of events, the three routes taking turns for
+    three rounds; the ratios come from those windows. Then (d) KnitReducer.with_readout_error on syc 32 5 end to end
+    and a marginal of 10 clbits of the reducer it returns, beside the same marginal of the base reducer."""
+    import numpy as np
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine, observables as ob
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+
+    res = {"config": "syc_32_5_p2", "device": torch.cuda.get_device_name(0), "reps": 20}
+    ctx = engine.get_context(0)
+    m, calls, rounds = 16, 50, 3
+    passes = len(ob.wht_pass_bits(m))
+    rng = np.random.default_rng(0)
+    mats = np.stack([ob.readout_matrix(e0, e1) for e0, e1 in rng.uniform(0.01, 0.05, size=(m, 2))])
+    mats_d = [torch.from_numpy(A).cuda() for A in mats]
+
+    def torch_route(src):
+        x = src
+        for b in range(m):
+            x = torch.einsum("yx,axb->ayb", mats_d[b], x.reshape(-1, 2, 1 << b))
+        return x.reshape(src.shape)
+
+    for rows in (64, 256):
+        src = torch.randn((rows, 1 << m), dtype=torch.float64, device="cuda")
+        dst, buf = torch.empty_like(src), src.clone()
+        entry = {"rows": rows, "m": m, "passes": passes, "non_identity_bits": m,
+                 "bytes_moved": 2 * passes * rows * (1 << m) * 8, "flops": 3 * m * rows * (1 << m)}
+        routes = {"qk_kron2_rows": lambda: engine.kron2_rows(ctx, src, mats, m, out=dst),
+                  "qk_wht_rows": lambda: engine.wht_rows(ctx, src, m, out=dst),
+                  "torch_einsum_per_bit": lambda: torch_route(src)}
+        for name, fn in routes.items():
+            entry[f"{name}_out_of_place"] = timed(torch, fn)
+        entry["qk_kron2_rows_in_place"] = timed(torch, lambda: engine.kron2_rows(ctx, buf, mats, m, out=buf))
+        buf.copy_(src)
+        entry["qk_wht_rows_in_place"] = timed(torch, lambda: engine.wht_rows(ctx, buf, m, out=buf))
+        windows = {name: [] for name in routes}
+        for _ in range(rounds):  # the routes take turns
+            for name, fn in routes.items():
+                t = timed(torch, lambda: [fn() for _ in range(calls)], reps=7, warm=1)
+                windows[name].append(t["median_ms"] / calls)
+        for name, per_call in windows.items():
+            per_call.sort()
+            entry[f"{name}_per_call_in_{calls}_call_windows"] = {"median_ms": per_call[len(per_call) // 2],
+                                                                "min_ms": per_call[0], "max_ms": per_call[-1]}
+        k = entry[f"qk_kron2_rows_per_call_in_{calls}_call_windows"]
+        k["GBs"] = entry["bytes_moved"] / k["median_ms"] / 1e6
+        k["GFLOPs"] = entry["flops"] / k["median_ms"] / 1e6
+        w = entry[f"qk_wht_rows_per_call_in_{calls}_call_windows"]
+        w["GBs"] = entry["bytes_moved"] / w["median_ms"] / 1e6
+        entry["kron2_over_wht"] = k["median_ms"] / w["median_ms"]
+        entry["torch_over_kron2"] = entry[f"torch_einsum_per_bit_per_call_in_{calls}_call_windows"]["median_ms"] / k["median_ms"]
+        engine.kron2_rows(ctx, src, mats, m, out=dst)
+        entry["max_abs_diff_vs_torch"] = float((dst - torch_route(src)).abs().max())
+        res[f"rows_{rows}"] = entry
+        print(rows, json.dumps(entry), flush=True)
+
+    _, cut, _ = cutting.config_cut_circuit("syc", 32, 5, 2)
+    red = KnitReducer(VirtualCircuit(cut))
+    res["fragments"] = [{"rows": int(q.shape[0]), "m": len(cl)} for q, cl in zip(red.qs, red.clbits)]
+    res["terms"] = int(red.ops.num_terms)
+    confusion = np.stack([ob.readout_matrix(e0, e1) for e0, e1 in rng.uniform(0.01, 0.05, size=(red.N, 2))])
+    clbits = [0, 3, 5, 9, 14, 16, 20, 23, 27, 31]
+    res["with_readout_error"] = timed(torch, lambda: red.with_readout_error(confusion))
+    res["with_readout_mitigation"] = timed(torch, lambda: red.with_readout_mitigation(confusion))
+    noisy = red.with_readout_error(confusion)
+    res["rows_bytes"] = int(sum(q.numel() * 8 for q in noisy.qs))
+    res["marginal_10_after_readout_error"] = timed(torch, lambda: noisy.marginal(clbits))
+    res["marginal_10_base"] = timed(torch, lambda: red.marginal(clbits))
+    undone = noisy.with_readout_mitigation(confusion)
+    res["check"] = {"mass_after_readout_error": float(noisy.expectation([0])[0]),
+                    "mitigation_of_error_vs_base_marginal_max_abs_diff": float(
+                        (undone.marginal(clbits) - red.marginal(clbits)).abs().max())}
+    print(json.dumps(res, indent=1), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--channels", action="store_true", help="the per-clbit channels leg only (see channels_leg)")
     ap.add_argument("--scan", action="store_true", help="the streamed-scan leg only (see scan_leg)")
     ap.add_argument("--moments", action="store_true", help="the second-moments leg only (see moments_leg)")
     ap.add_argument("--lookup", action="store_true", help="the probabilities-at-chosen-keys leg only (see lookup_leg)")
@@ -491,6 +582,8 @@ def main():
         return moments_leg(args)
     if args.scan:
         return scan_leg(args)
+    if args.channels:
+        return channels_leg(args)
     import torch
 
     from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine
