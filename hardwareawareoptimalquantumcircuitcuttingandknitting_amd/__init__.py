@@ -29,6 +29,7 @@ from .virtual_gates import (
 from .virtual_circuit import VirtualCircuit, generate_instantiations
 from .run import (RunTimeInfo, run_virtual_circuit, run_virtual_circuit_collision, run_virtual_circuit_dense,
                   run_virtual_circuit_expectation, run_virtual_circuit_fidelity, run_virtual_circuit_marginal,
+                  run_virtual_circuit_npd,
                   run_virtual_circuit_overlap, run_virtual_circuit_probabilities, run_virtual_circuit_scan,
                   run_virtual_circuit_shots, run_virtual_circuit_top_k, run_virtual_circuit_xeb)
 
@@ -40,5 +41,5 @@ __all__ = [
     "run_virtual_circuit_marginal", "run_virtual_circuit_expectation", "run_virtual_circuit_shots",
     "run_virtual_circuit_probabilities", "run_virtual_circuit_xeb", "run_virtual_circuit_collision",
     "run_virtual_circuit_overlap", "run_virtual_circuit_scan", "run_virtual_circuit_top_k",
-    "run_virtual_circuit_fidelity",
+    "run_virtual_circuit_fidelity", "run_virtual_circuit_npd",
 ]

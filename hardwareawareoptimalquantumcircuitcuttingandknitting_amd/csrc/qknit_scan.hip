@@ -6,6 +6,9 @@
 //                     indices (i << mb | j), counts and a histogram of binades; with a second knit R' on the same
 //                     (i, j) also the cross terms (sum R R', Hellinger sum, L1 and max difference).
 //   qk_knit_collect   the same mainloop; appends (flat index, R) of every output with R > tau.
+//   qk_knit_project_scan  the same mainloop; one pass of the nearest-probability-distribution iteration: sums and
+//                     counts of the members (|R| > accuracy) and of the kept (R > max(theta, accuracy)), and the
+//                     statistics of p = R - theta on the kept; with a second knit also of p' and of the pair.
 //
 // Layout. A workgroup of 256 threads forms one 128 x 128 tile of R: 2 x 2 waves of 64 x 64 = 4 x 4
 // v_mfma_f64_16x16x4_f64 blocks each, K streamed in chunks of 16 rows through a double-buffered LDS stage
@@ -372,6 +375,232 @@ __global__ __launch_bounds__(SC_THREADS, 2) void knit_collect_kernel(ScanArgs a)
     }
 }
 
+// ---- one pass of the nearest-probability-distribution iteration ("Nearest probability
+// distribution"): the scan's mainloop, another epilogue. The single-knit variant carries the six slots of the first
+// knit only; the pair variant all fifteen.
+constexpr int PJ_SLOTS = QK_PROJ_NSTATS;
+constexpr int PJ_SINGLE = QK_PROJ_PMAX + 1;
+constexpr int PJ_PAIR = QK_PROJ_MAXD + 1;
+
+struct ProjArgs {
+    int K;
+    const double* __restrict__ A;
+    int64_t lda;
+    const double* __restrict__ B;
+    int64_t ldb;
+    int K2;
+    const double* __restrict__ A2;
+    int64_t lda2;
+    const double* __restrict__ B2;
+    int64_t ldb2;
+    int64_t i_begin, i_end, N;
+    int mb;
+    sc_shape sh;
+    double accuracy, theta, lower, theta2, lower2;  // lower = max(theta, accuracy)
+    double* __restrict__ pstats;              // [PJ_SLOTS][groups]
+    int64_t* __restrict__ pidx;               // [groups]: flat index of the workgroup's PMAX
+    int ent_slot;                             // knit_project_entropy_kernel: the slot it fills
+    unsigned long long* __restrict__ counts;  // NMEMBER, NKEPT, NMEMBER2, NKEPT2 (zeroed before the launch)
+};
+
+__device__ __forceinline__ bool pj_is_max(int s) {
+    return s == QK_PROJ_PMAX || s == QK_PROJ_PMAX2 || s == QK_PROJ_MAXD;
+}
+
+// Everything but the entropy slots. The counts leave the registers after every tile (a wave sum, then one LDS
+// atomic per wave) and the pair variant's sums wait in LDS while the mainloop runs, so that neither holds vector
+// registers across it.
+template <bool PAIR>
+__global__ __launch_bounds__(SC_THREADS, PAIR ? 1 : 2) void knit_project_kernel(ProjArgs a) {
+    constexpr int NS = PAIR ? PJ_PAIR : PJ_SINGLE;
+    constexpr int NPARK = PAIR ? NS : 0;
+    __shared__ __attribute__((aligned(16))) double As[2][SC_K][SC_PITCH];
+    __shared__ __attribute__((aligned(16))) double Bs[2][SC_K][SC_PITCH];
+    __shared__ double park[NPARK ? NPARK : 1][SC_THREADS];
+    __shared__ unsigned long long scount[4];
+    __shared__ unsigned long long sarg;
+    static_assert(sizeof(As) >= sizeof(double) * PJ_PAIR * SC_THREADS, "the reduction scratch aliases As");
+    const int tid = threadIdx.x;
+    if (tid < 4) scount[tid] = 0;
+    if (tid == 0) sarg = ~0ull;
+    double st[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) st[s] = 0.0;
+    st[QK_PROJ_PMAX] = -INFINITY;  // every output has a p >= 0: the first one replaces it
+    int64_t imax = INT64_MAX;
+    int buf = 0;
+#pragma unroll
+    for (int s = 0; s < NPARK; ++s) park[s][tid] = st[s];
+    __syncthreads();
+
+    for (int64_t t = blockIdx.x; t < a.sh.tiles; t += gridDim.x) {
+        const int64_t m0 = a.i_begin + (t / a.sh.tiles_n) * SC_T, n0 = (t % a.sh.tiles_n) * SC_T;
+        sc_d4 acc[4][4];
+        sc_d4 acc2[PAIR ? 4 : 1][PAIR ? 4 : 1];
+        if constexpr (PAIR) {
+            sc_tile(a.A2, a.lda2, a.B2, a.ldb2, a.K2, m0, a.i_end, n0, a.N, acc2, As, Bs, buf);
+        }
+        sc_tile(a.A, a.lda, a.B, a.ldb, a.K, m0, a.i_end, n0, a.N, acc, As, Bs, buf);
+#pragma unroll
+        for (int s = 0; s < NPARK; ++s) st[s] = park[s][tid];
+        unsigned cnt[PAIR ? 2 : 1] = {};  // of this tile, per knit: members (at most 64) | kept << 16
+        bool cok[4];
+        int64_t col[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            col[j] = sc_col(n0, j);
+            cok[j] = col[j] < a.N;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int64_t row = sc_row(m0, i, r);
+                    if (!(row < a.i_end && cok[j])) continue;
+                    const double v = acc[i][j][r];
+                    const int64_t flat = (row << a.mb) | col[j];
+                    const bool mem = fabs(v) > a.accuracy, kept = v > a.lower;
+                    const double p = kept ? v - a.theta : 0.0;
+                    st[QK_PROJ_MSUM] += mem ? v : 0.0;
+                    st[QK_PROJ_TSUM] += kept ? v : 0.0;
+                    st[QK_PROJ_PSUM] += p;
+                    st[QK_PROJ_PSQ] = fma(p, p, st[QK_PROJ_PSQ]);
+                    if (p > st[QK_PROJ_PMAX] || (p == st[QK_PROJ_PMAX] && flat < imax)) {
+                        st[QK_PROJ_PMAX] = p;
+                        imax = flat;
+                    }
+                    cnt[0] += (mem ? 1u : 0u) | (kept ? 0x10000u : 0u);
+                    if constexpr (PAIR) {
+                        const double w = acc2[i][j][r];
+                        const bool mem2 = fabs(w) > a.accuracy, kept2 = w > a.lower2;
+                        const double q = kept2 ? w - a.theta2 : 0.0;
+                        const double d = fabs(p - q);
+                        st[QK_PROJ_MSUM2] += mem2 ? w : 0.0;
+                        st[QK_PROJ_TSUM2] += kept2 ? w : 0.0;
+                        st[QK_PROJ_PSUM2] += q;
+                        st[QK_PROJ_PSQ2] = fma(q, q, st[QK_PROJ_PSQ2]);
+                        st[QK_PROJ_PMAX2] = q > st[QK_PROJ_PMAX2] ? q : st[QK_PROJ_PMAX2];
+                        st[QK_PROJ_HELL] += sqrt(p * q);
+                        st[QK_PROJ_L1D] += d;
+                        st[QK_PROJ_MAXD] = d > st[QK_PROJ_MAXD] ? d : st[QK_PROJ_MAXD];
+                        cnt[1] += (mem2 ? 1u : 0u) | (kept2 ? 0x10000u : 0u);
+                    }
+                }
+#pragma unroll
+        for (int c = 0; c < (PAIR ? 2 : 1); ++c) {
+            unsigned n = cnt[c];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);  // of the wave: at most 4096 in either half
+            if ((tid & 63) == 0 && n) {
+                atomicAdd(&scount[2 * c], (unsigned long long)(n & 0xffffu));
+                atomicAdd(&scount[2 * c + 1], (unsigned long long)(n >> 16));
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < NPARK; ++s) park[s][tid] = st[s];
+    }
+
+    // workgroup: the scan's halving tree; the index of PMAX by an integer minimum over the threads that hold it
+    __syncthreads();  // the last tile's LDS reads are done: As becomes the scratch
+    double(*red)[SC_THREADS] = reinterpret_cast<double(*)[SC_THREADS]>(&As[0][0][0]);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) red[s][tid] = st[s];
+    __syncthreads();
+    for (int h = SC_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const double x = red[s][tid], y = red[s][tid + h];
+                red[s][tid] = pj_is_max(s) ? (y > x ? y : x) : x + y;
+            }
+        }
+        __syncthreads();
+    }
+    if (st[QK_PROJ_PMAX] == red[QK_PROJ_PMAX][0]) atomicMin(&sarg, (unsigned long long)imax);
+    __syncthreads();
+    const int64_t G = gridDim.x, g = blockIdx.x;
+    if (tid < NS && tid != QK_PROJ_PENT && tid != QK_PROJ_PENT2) a.pstats[tid * G + g] = red[tid][0];
+    if (tid == 0) a.pidx[g] = (int64_t)sarg;
+    if (tid < 4 && scount[tid]) atomicAdd(&a.counts[tid], scount[tid]);
+}
+
+// One entropy slot (PENT of the first knit, or PENT2 of the second: the entry passes that knit as the first, its
+// theta and `ent_slot`), in a launch of its own: the logarithm beside the other sums does not fit the registers
+// that the mainloop leaves.
+__global__ __launch_bounds__(SC_THREADS, 2) void knit_project_entropy_kernel(ProjArgs a) {
+    __shared__ __attribute__((aligned(16))) double As[2][SC_K][SC_PITCH];
+    __shared__ __attribute__((aligned(16))) double Bs[2][SC_K][SC_PITCH];
+    const int tid = threadIdx.x;
+    double ent = 0.0;
+    int buf = 0;
+    for (int64_t t = blockIdx.x; t < a.sh.tiles; t += gridDim.x) {
+        const int64_t m0 = a.i_begin + (t / a.sh.tiles_n) * SC_T, n0 = (t % a.sh.tiles_n) * SC_T;
+        sc_d4 acc[4][4];
+        sc_tile(a.A, a.lda, a.B, a.ldb, a.K, m0, a.i_end, n0, a.N, acc, As, Bs, buf);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double v = acc[i][j][r];
+                    const bool kept = sc_row(m0, i, r) < a.i_end && sc_col(n0, j) < a.N && v > a.lower;
+                    const double p = kept ? v - a.theta : 0.0;
+                    ent += kept ? -(p * log(p)) : 0.0;
+                }
+    }
+    __syncthreads();  // the last tile's LDS reads are done: As becomes the scratch
+    double* red = &As[0][0][0];
+    red[tid] = ent;
+    __syncthreads();
+    for (int h = SC_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) red[tid] += red[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) a.pstats[a.ent_slot * (int64_t)gridDim.x + blockIdx.x] = red[0];
+}
+
+// stats[s] = the G partials of slot s combined in ascending workgroup order (slots past `slots` and the entropy
+// slots without the flag: 0.0); counts[QK_PROJ_ARGMAX] = the flat index of PMAX, the lowest among equal values.
+__global__ __launch_bounds__(SC_THREADS) void knit_project_stage2(int64_t G, const double* __restrict__ pstats,
+                                                                  const int64_t* __restrict__ pidx, int slots, int ent,
+                                                                  double* __restrict__ stats,
+                                                                  int64_t* __restrict__ counts) {
+    __shared__ double sv[PJ_SLOTS][SC_MAX_GROUPS];
+    __shared__ int64_t si[SC_MAX_GROUPS];
+    const int tid = threadIdx.x;
+    for (int64_t e = tid; e < slots * G; e += SC_THREADS) sv[e / G][e % G] = pstats[e];
+    for (int64_t e = tid; e < G; e += SC_THREADS) si[e] = pidx[e];
+    __syncthreads();
+    if (tid < PJ_SLOTS) {
+        const int s = tid;
+        double x = 0.0;
+        if (s < slots && !((s == QK_PROJ_PENT || s == QK_PROJ_PENT2) && !ent)) {
+            x = sv[s][0];
+            if (s == QK_PROJ_PMAX) {
+                int64_t at = si[0];
+                for (int64_t g = 1; g < G; ++g) {
+                    const double y = sv[s][g];
+                    if (y > x || (y == x && si[g] < at)) {
+                        x = y;
+                        at = si[g];
+                    }
+                }
+                counts[QK_PROJ_ARGMAX] = at;
+            } else if (pj_is_max(s)) {
+                for (int64_t g = 1; g < G; ++g) x = sv[s][g] > x ? sv[s][g] : x;
+            } else {
+                for (int64_t g = 1; g < G; ++g) x += sv[s][g];
+            }
+        }
+        stats[s] = x;
+    }
+}
+
+int64_t pj_work_bytes(const sc_shape& sh) { return sh.groups * (PJ_SLOTS + 1) * 8; }
+
 int sc_fail(qk_ctx* ctx, const char* msg) {
     if (ctx) ctx->err = msg;
     return QK_EARG;
@@ -489,6 +718,75 @@ int qk_knit_collect(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int
     a.count = reinterpret_cast<unsigned long long*>(count_dev);
     hipLaunchKernelGGL(knit_collect_kernel, dim3((unsigned)a.sh.groups), dim3(SC_THREADS), 0, ctx->stream, a);
     return sc_hip(ctx, hipGetLastError(), "knit_collect_kernel");
+}
+
+int qk_knit_project_scan_workspace_bytes(int ma, int mb, int64_t i_begin, int64_t i_end, int64_t* bytes) {
+    if (!bytes || ma < 0 || ma > 30 || mb < 0 || mb > 30 || i_begin < 0 || i_begin >= i_end ||
+        i_end > ((int64_t)1 << ma))
+        return QK_EARG;
+    *bytes = pj_work_bytes(sc_make_shape(mb, i_begin, i_end));
+    return QK_OK;
+}
+
+int qk_knit_project_scan(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int64_t lda, const double* B,
+                         int64_t ldb, int64_t K2, const double* A2, int64_t lda2, const double* B2, int64_t ldb2,
+                         int64_t i_begin, int64_t i_end, int flags, double theta, double theta2, double accuracy,
+                         double* stats, int64_t* counts, void* work, int64_t work_bytes) {
+    if (!ctx) return QK_EARG;
+    std::string msg;
+    if (const char* bad = sc_check(K, ma, mb, A, lda, B, ldb, i_begin, i_end, 0.0)) {
+        msg = std::string("qk_knit_project_scan: ") + bad;
+        return sc_fail(ctx, msg.c_str());
+    }
+    if (K2 < 0) return sc_fail(ctx, "qk_knit_project_scan: K2 must not be negative");
+    if (K2 > 0) {
+        if (const char* bad = sc_check(K2, ma, mb, A2, lda2, B2, ldb2, i_begin, i_end, 0.0)) {
+            msg = std::string("qk_knit_project_scan (second knit): ") + bad;
+            return sc_fail(ctx, msg.c_str());
+        }
+    }
+    if (flags & ~QK_PROJ_ENTROPY) return sc_fail(ctx, "qk_knit_project_scan: unknown flag");
+    if (!(theta >= 0.0) || !(theta2 >= 0.0) || !(accuracy >= 0.0))  // a NaN fails every comparison
+        return sc_fail(ctx, "qk_knit_project_scan: theta, theta2 and accuracy must be numbers >= 0");
+    if (!stats || !counts) return sc_fail(ctx, "qk_knit_project_scan: null stats or counts");
+    const sc_shape sh = sc_make_shape(mb, i_begin, i_end);
+    if (!work || work_bytes < pj_work_bytes(sh))
+        return sc_fail(ctx, "qk_knit_project_scan: workspace too small (qk_knit_project_scan_workspace_bytes)");
+    int rc = sc_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (rc) return rc;
+    rc = sc_hip(ctx, hipMemsetAsync(counts, 0, QK_PROJ_NCOUNTS * sizeof(int64_t), ctx->stream), "hipMemsetAsync");
+    if (rc) return rc;
+    ProjArgs a{};
+    a.K = (int)K; a.A = A; a.lda = lda; a.B = B; a.ldb = ldb;
+    a.K2 = (int)K2; a.A2 = A2; a.lda2 = lda2; a.B2 = B2; a.ldb2 = ldb2;
+    a.i_begin = i_begin; a.i_end = i_end; a.N = (int64_t)1 << mb; a.mb = mb;
+    a.sh = sh;
+    a.accuracy = accuracy; a.theta = theta; a.lower = theta > accuracy ? theta : accuracy;
+    a.theta2 = theta2; a.lower2 = theta2 > accuracy ? theta2 : accuracy;
+    a.pstats = static_cast<double*>(work);
+    a.pidx = reinterpret_cast<int64_t*>(a.pstats + PJ_SLOTS * sh.groups);
+    a.counts = reinterpret_cast<unsigned long long*>(counts);
+    const dim3 grid((unsigned)sh.groups), block(SC_THREADS);
+    const bool ent = flags & QK_PROJ_ENTROPY, pair = K2 > 0;
+    if (ent) {
+        a.ent_slot = QK_PROJ_PENT;
+        hipLaunchKernelGGL(knit_project_entropy_kernel, grid, block, 0, ctx->stream, a);
+        if (pair) {
+            ProjArgs b = a;
+            b.K = a.K2; b.A = A2; b.lda = lda2; b.B = B2; b.ldb = ldb2;
+            b.theta = a.theta2; b.lower = a.lower2; b.ent_slot = QK_PROJ_PENT2;
+            hipLaunchKernelGGL(knit_project_entropy_kernel, grid, block, 0, ctx->stream, b);
+        }
+        rc = sc_hip(ctx, hipGetLastError(), "knit_project_entropy_kernel");
+        if (rc) return rc;
+    }
+    if (pair) hipLaunchKernelGGL(knit_project_kernel<true>, grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL(knit_project_kernel<false>, grid, block, 0, ctx->stream, a);
+    rc = sc_hip(ctx, hipGetLastError(), "knit_project_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(knit_project_stage2, dim3(1), block, 0, ctx->stream, sh.groups, a.pstats, a.pidx,
+                       pair ? PJ_PAIR : PJ_SINGLE, ent ? 1 : 0, stats, counts);
+    return sc_hip(ctx, hipGetLastError(), "knit_project_stage2");
 }
 
 }  // extern "C"

@@ -1015,6 +1015,79 @@ def knit_collect(ctx: Context, A, B, tau: float, capacity: int):
     return idx[:used], vals[:used], total
 
 
+PROJ_STATS = ("msum", "tsum", "psum", "psq", "pent", "pmax", "msum2", "tsum2", "psum2", "psq2", "pent2", "pmax2",
+              "hell", "l1d", "maxd")  # QK_PROJ_*
+PROJ_COUNTS = ("nmember", "nkept", "nmember2", "nkept2")
+_PROJ_NSTATS, _PROJ_NCOUNTS, _PROJ_ENTROPY, _PROJ_ARGMAX = 16, 5, 1, 4
+
+
+def check_projection_args(theta: float, theta2: float, accuracy: float) -> tuple:
+    """``(theta, theta2, accuracy)`` as floats; ``ValueError`` for a NaN or a negative one."""
+    vals = tuple(float(v) for v in (theta, theta2, accuracy))
+    for name, v in zip(("theta", "theta2", "accuracy"), vals):
+        if not v >= 0.0:
+            raise ValueError(f"{name} must be a number >= 0, not {v}")
+    return vals
+
+
+def knit_project_scan(ctx: Context, A, B, A2=None, B2=None, *, theta: float = 0.0, theta2: float = 0.0,
+                      accuracy: float = 0.0, entropy: bool = False) -> dict:
+    """``qk_knit_project_scan``: one pass of the nearest-probability-distribution iteration over the knit of ``A``
+    and ``B`` (operands as :func:`knit_scan`), without forming it. With ``v`` an output: ``member = |v| > accuracy``,
+    ``kept = v > max(theta, accuracy)`` (strict), ``p = v - theta`` on the kept and 0 elsewhere. Returns a dict of
+    Python floats named as ``PROJ_STATS``: ``msum`` (sum of ``v`` over the members), ``tsum`` (sum of ``v`` over the
+    kept), ``psum``, ``psq``, ``pent`` (``sum -p ln p``, only with ``entropy=True``, else 0.0), ``pmax``; with a
+    second knit ``A2`` / ``B2`` and its own ``theta2`` the same six of ``p'`` (``msum2`` ...) and ``hell`` =
+    ``sum sqrt(p p')``, ``l1d`` = ``sum |p - p'|``, ``maxd`` (else 0.0); the ints ``nmember``, ``nkept``
+    (``nmember2``, ``nkept2``) and ``argmax``, the flat index of ``pmax``, the lowest among equal values. Side A is
+    walked in slabs of at most ``SCAN_SLAB_OUTPUTS`` outputs; the slabs are combined in ascending order in float64
+    on the host."""
+    T = torch()
+    K, ma, lda = _scan_side("A", A)
+    _, mb, ldb = _scan_side("B", B, K)
+    pair = A2 is not None or B2 is not None
+    K2 = lda2 = ldb2 = 0
+    if pair:
+        if A2 is None or B2 is None:
+            raise ValueError("a second knit needs both A2 and B2")
+        K2, ma2, lda2 = _scan_side("A2", A2)
+        _, mb2, ldb2 = _scan_side("B2", B2, K2)
+        if (ma2, mb2) != (ma, mb) or A2.device != A.device or B2.device != A.device:
+            raise ValueError(f"the second knit is 2^{ma2} x 2^{mb2}, the first 2^{ma} x 2^{mb} (or another device)")
+    if B.device != A.device:
+        raise ValueError("A and B must be on one device")
+    theta, theta2, accuracy = check_projection_args(theta, theta2, accuracy)
+    slabs = scan_slabs(ma, mb)
+    dev = A.device
+    stats = T.empty((len(slabs), _PROJ_NSTATS), dtype=T.float64, device=dev)
+    counts = T.empty((len(slabs), _PROJ_NCOUNTS), dtype=T.int64, device=dev)
+    need = ctypes.c_int64()
+    ctx.check(ctx.lib.qk_knit_project_scan_workspace_bytes(ma, mb, *slabs[0], ctypes.byref(need)),
+              "qk_knit_project_scan_workspace_bytes")
+    work = T.empty(need.value // 8, dtype=T.float64, device=dev)  # the first slab is the largest
+    for s, (i0, i1) in enumerate(slabs):
+        ctx.check(ctx.lib.qk_knit_project_scan(ctx.handle, K, ma, mb, A.data_ptr(), lda, B.data_ptr(), ldb, K2, _ptr(A2),
+                                               lda2, _ptr(B2), ldb2, i0, i1, _PROJ_ENTROPY if entropy else 0, theta,
+                                               theta2, accuracy, stats[s].data_ptr(), counts[s].data_ptr(),
+                                               work.data_ptr(), need.value), "qk_knit_project_scan")
+    st, ct = stats.cpu().numpy(), counts.cpu().numpy()
+    out = {}
+    for slot, name in enumerate(PROJ_STATS):
+        col = st[:, slot]
+        if name in ("pmax", "pmax2", "maxd"):
+            out[name] = float(col.max())
+        else:
+            acc = np.float64(0.0)
+            for v in col:  # ascending slabs
+                acc = acc + v
+            out[name] = float(acc)
+    for slot, name in enumerate(PROJ_COUNTS):
+        out[name] = int(ct[:, slot].sum())
+    # the slabs ascend in flat index: the first slab that holds the maximum holds its lowest index
+    out["argmax"] = int(ct[int(np.argmax(st[:, PROJ_STATS.index("pmax")])), _PROJ_ARGMAX])
+    return out
+
+
 # ----------------------------------------------------------------------------- shot sampling
 _SEED_STRIDE = 0x632BE59BD9B4E019  # per-fragment stream offset (mirrored by oracle/sampling.py)
 _U64 = (1 << 64) - 1

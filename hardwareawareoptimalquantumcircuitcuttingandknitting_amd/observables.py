@@ -586,6 +586,100 @@ def histogram_threshold(hist, k: int) -> tuple:
     return float(np.nextafter(np.ldexp(1.0, -b), 0.0)), int(cum[b])
 
 
+# ----------------------------------------------------------------------------- nearest probability distribution
+def project_scan_shape(ma: int, mb: int, i_begin: int = 0, i_end: int | None = None) -> dict:
+    """:func:`scan_shape` for ``qk_knit_project_scan``: the same decomposition; the workspace holds 16 partial sums
+    and one index per workgroup."""
+    sh = scan_shape(ma, mb, i_begin, i_end)
+    sh["workspace_bytes"] = sh["groups"] * 17 * 8
+    return sh
+
+
+def project_scan_host(Xs: list, Ys: list | None = None, theta: float = 0.0, theta2: float = 0.0,
+                      accuracy: float = 0.0) -> dict:
+    """numpy model of ``qk_knit_project_scan`` in ``np.longdouble``, named as :func:`engine.knit_project_scan` names
+    them; the knit and the flat index as in :func:`knit_scan_host`. ``member = |v| > accuracy``,
+    ``kept = v > max(theta, accuracy)`` (strict: an entry exactly at ``theta`` or at ``accuracy`` is not kept, one at
+    ``-accuracy`` and an exact zero are not members), ``p = v - theta`` on the kept, else 0. ``values`` / ``values2``
+    hold ``p`` / ``p'``."""
+    theta, theta2, accuracy = engine.check_projection_args(theta, theta2, accuracy)
+
+    def one(Zs, th):
+        R = knit_scan_host(Zs)["values"]
+        member, kept = np.abs(R) > accuracy, R > max(th, accuracy)
+        p = np.where(kept, R - np.longdouble(th), np.longdouble(0))
+        lnp = np.log(p, where=kept, out=np.zeros_like(p))
+        return p, dict(msum=R[member].sum(), tsum=R[kept].sum(), psum=p.sum(), psq=(p * p).sum(), pent=-(p * lnp).sum(),
+                       pmax=p.max(), nmember=int(member.sum()), nkept=int(kept.sum()))
+
+    p, out = one(Xs, theta)
+    out.update(argmax=int(np.argmax(p)), values=p, hell=0.0, l1d=0.0, maxd=0.0, nmember2=0, nkept2=0)
+    out.update({name + "2": 0.0 for name in ("msum", "tsum", "psum", "psq", "pent", "pmax")})
+    if Ys is not None:
+        if len(Ys) != len(Xs) or any(np.asarray(X).shape[1] != np.asarray(Y).shape[1] for X, Y in zip(Xs, Ys)):
+            raise ValueError("the two knits have different fragments")
+        q, second = one(Ys, theta2)
+        out.update({name + "2": v for name, v in second.items()})
+        out.update(hell=np.sqrt(p * q).sum(), l1d=np.abs(p - q).sum(), maxd=np.abs(p - q).max(), values2=q)
+    return out
+
+
+@dataclass
+class ProjectionThreshold:
+    """What :func:`projection_threshold` returns. ``msum`` / ``tsum``: the last evaluation's."""
+    theta: float
+    kept: int
+    passes: int
+    msum: float
+    tsum: float
+
+
+def projection_threshold(evaluate, max_passes: int = 32) -> ProjectionThreshold:
+    """The threshold of ``nearest_probability_distribution`` (``quasi_distr.py:28-43``) by Newton's (Michelot's)
+    iteration. ``evaluate(theta) -> (MSUM, TSUM, NKEPT)``: the sum of the members, and the sum and the number of the
+    kept entries (those above ``theta``). The projection keeps ``v - theta`` on ``{v > theta}`` with ``theta`` such
+    that the kept values sum to ``MSUM``: ``f(theta) = TSUM - theta NKEPT - MSUM`` is convex, piecewise linear and
+    decreasing with ``f(0) >= 0``, so ``theta <- (TSUM - MSUM) / NKEPT`` from 0 rises monotonically, never passes
+    the root and has reached it when ``NKEPT`` stops changing. ``MSUM <= 0``, or no kept entry at some pass, is the
+    empty projection: ``kept = 0``, ``theta = inf``. ``RuntimeError`` after ``max_passes`` evaluations."""
+    theta, last = 0.0, None
+    for passes in range(1, int(max_passes) + 1):
+        msum, tsum, kept = evaluate(theta)
+        msum, tsum, kept = float(msum), float(tsum), int(kept)
+        if not msum > 0.0 or kept == 0:
+            return ProjectionThreshold(float("inf"), 0, passes, msum, 0.0)
+        if kept == last:
+            return ProjectionThreshold(theta, kept, passes, msum, tsum)
+        theta, last = (tsum - msum) / kept, kept
+    raise RuntimeError(f"the projection threshold did not settle in {max_passes} passes (theta = {theta!r}, "
+                       f"{last} kept)")
+
+
+@dataclass
+class KnitProjection:
+    """What :meth:`KnitReducer.project` returns: the nearest probability distribution of the knit ``R`` (of its
+    marginal onto ``clbits``) is ``R - theta`` on ``{R > max(theta, accuracy)}`` and 0 elsewhere."""
+    theta: float         # inf: the empty projection (mass <= 0)
+    accuracy: float      # the truncation: only |R| > accuracy are members
+    mass: float          # MSUM: the sum of the members, which the kept entries' projections sum to
+    kept: int            # entries of the projection
+    members: int
+    dropped_mass: float  # MSUM - TSUM: the sum of the members that are not kept, spread over the kept ones
+    passes: int          # kernel passes the iteration took
+    clbits: list         # bit i of a key is clbits[i]
+
+
+@dataclass
+class ProjectedScan:
+    """What :meth:`KnitReducer.projected_scan` returns: statistics of the projection ``p``."""
+    mass: float             # sum p
+    collision: float        # sum p^2
+    shannon_entropy: float  # bits, of p / sum p (nan without the entropy term or with nothing kept)
+    max: float
+    argmax: int | None      # key of the maximum, the lowest flat index among equal values; None with nothing kept
+    support: int            # kept entries
+
+
 def _side_operand(ctx, parts: list, K: int, dev):
     """One side of the scan from ``parts = [X_f [K, 2^w_f], ...]``: their Khatri-Rao product, the first part in the
     lowest bits; parts of one column only scale the rows; no part at all is a column of ones."""
@@ -1255,6 +1349,127 @@ class KnitReducer:
     def max_difference(self, other, clbits=None) -> float:
         """``max |R_S - R'_S|`` (one pair scan; arguments as :meth:`hellinger_fidelity`)."""
         return self._pair_scan(other, clbits)["maxd"]
+
+    # -- the nearest probability distribution ---------------------------------------------------
+    def project(self, clbits=None, *, accuracy: float = 0.0, max_passes: int = 32) -> KnitProjection:
+        """The nearest probability distribution of the knit (``clbits``: of its marginal onto them), the reference's
+        ``nearest_probability_distribution`` of the entries with ``|R| > accuracy``, without the 2^N output: the
+        threshold by :func:`projection_threshold`, one ``qk_knit_project_scan`` pass per step (DESIGN.md §4a
+        "Nearest probability distribution"). Keys on clbits that no fragment measures hold exact zeros and are never
+        members. With no fragment at all there is one outcome at key 0."""
+        self.ctx.bind_stream()
+        cl = self._scan_clbits(clbits)
+        _, _, accuracy = engine.check_projection_args(0.0, 0.0, accuracy)
+        A, B, _, _, _, _ = self._scan_operands(cl)
+        seen = {}
+
+        def evaluate(theta):
+            seen.update(engine.knit_project_scan(self.ctx, A, B, theta=theta, accuracy=accuracy))
+            return seen["msum"], seen["tsum"], seen["nkept"]
+
+        th = projection_threshold(evaluate, max_passes)
+        return KnitProjection(theta=th.theta, accuracy=accuracy, mass=th.msum, kept=th.kept, members=seen["nmember"],
+                              dropped_mass=th.msum - th.tsum, passes=th.passes, clbits=cl)
+
+    @staticmethod
+    def _check_projection(projection) -> float:
+        """The lower bound ``max(theta, accuracy)`` of a projection's kept entries."""
+        if not isinstance(projection, KnitProjection):
+            raise ValueError("projection must be a KnitProjection (KnitReducer.project)")
+        theta, _, accuracy = engine.check_projection_args(projection.theta, 0.0, projection.accuracy)
+        return max(theta, accuracy)
+
+    def projected_probabilities(self, keys, projection: KnitProjection):
+        """Device fp64 ``[M]``: the projection at the given keys, :meth:`probabilities` (over the projection's
+        clbits) mapped through ``R > max(theta, accuracy) ? R - theta : 0`` on the device."""
+        lower = self._check_projection(projection)
+        R = self.probabilities(keys, projection.clbits)
+        T = engine.torch()
+        return T.where(R > lower, R - projection.theta, T.zeros_like(R))
+
+    def projected_scan(self, projection: KnitProjection, *, entropy: bool = True) -> ProjectedScan:
+        """Statistics of the projection: one ``qk_knit_project_scan`` pass at the final threshold (with
+        ``entropy``, one more launch of the mainloop for the logarithms)."""
+        self._check_projection(projection)
+        self.ctx.bind_stream()
+        A, B, wa, wb, _, _ = self._scan_operands(projection.clbits)
+        st = engine.knit_project_scan(self.ctx, A, B, theta=projection.theta, accuracy=projection.accuracy,
+                                      entropy=entropy)
+        P = st["psum"]
+        H = (st["pent"] / P + np.log(P)) / np.log(2.0) if entropy and st["nkept"] and P > 0 else float("nan")
+        key = int(self._scan_key(st["argmax"], len(wb), wa, wb)) if st["nkept"] else None
+        return ProjectedScan(mass=P, collision=st["psq"], shannon_entropy=float(H), max=st["pmax"], argmax=key,
+                             support=st["nkept"])
+
+    def projected_heavy_outputs(self, projection: KnitProjection, min_value: float = 0.0,
+                                capacity: int = 1 << 24) -> tuple:
+        """Device ``(keys, values)`` of every entry of the projection with a value above ``min_value >= 0``
+        (strict; 0: every kept entry), sorted as :meth:`heavy_outputs`: ``qk_knit_collect`` at
+        ``max(theta, accuracy, theta + min_value)``, then the shift. ``ValueError``, naming the count, when more
+        than ``capacity`` entries qualify."""
+        lower = self._check_projection(projection)
+        if not float(min_value) >= 0:
+            raise ValueError(f"min_value must not be negative, not {min_value}")
+        self.ctx.bind_stream()
+        A, B, wa, wb, _, _ = self._scan_operands(projection.clbits)
+        keys, vals = self._collect_sorted(A, B, wa, wb, max(lower, projection.theta + float(min_value)), int(capacity))
+        return keys, vals - projection.theta
+
+    def projected_top_k(self, k: int, projection: KnitProjection, capacity: int = 1 << 24) -> tuple:
+        """Device ``(keys, values)`` of the ``k`` largest entries of the projection (fewer when fewer are kept),
+        sorted as :meth:`heavy_outputs`: the route of :meth:`top_k` with its threshold raised to the kept set's
+        (the shift leaves the order of the entries as it is)."""
+        lower = self._check_projection(projection)
+        self.ctx.bind_stream()
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"k must not be negative, not {k}")
+        A, B, wa, wb, _, _ = self._scan_operands(projection.clbits)
+        st = engine.knit_scan(self.ctx, A, B, hist=True)
+        tau, count = histogram_threshold(st["hist"], k)
+        if tau < lower:
+            tau, count = lower, projection.kept
+        if count > capacity:
+            raise ValueError(f"{count} outcomes share the binades of the top {k}, more than capacity = {capacity}")
+        keys, vals = self._collect_sorted(A, B, wa, wb, tau, count)
+        return keys[:k], vals[:k] - projection.theta
+
+    def _projected_pair_scan(self, other, projection, other_projection, clbits) -> dict:
+        self._check_projection(projection)
+        self._check_projection(other_projection)
+        cl = list(projection.clbits) if clbits is None else check_clbits(clbits, self.N)
+        if cl != list(projection.clbits) or cl != list(other_projection.clbits):
+            raise ValueError(f"the projections are over clbits {projection.clbits} and {other_projection.clbits}, "
+                             f"the comparison over {cl}")
+        if projection.accuracy != other_projection.accuracy:
+            raise ValueError(f"the projections were truncated at {projection.accuracy} and "
+                             f"{other_projection.accuracy}: one pass takes one accuracy")
+        if not isinstance(other, KnitReducer):
+            raise ValueError("other must be a KnitReducer")
+        if other.N != self.N:
+            raise ValueError(f"{self.N} clbits against {other.N}")
+        if other.device != self.device:
+            raise ValueError(f"reducers on devices {self.device} and {other.device}")
+        self.ctx.bind_stream()
+        A, B, _, _, A2, B2 = self._scan_operands(cl, other)
+        return engine.knit_project_scan(self.ctx, A, B, A2, B2, theta=projection.theta, theta2=other_projection.theta,
+                                        accuracy=projection.accuracy)
+
+    def projected_hellinger_fidelity(self, other, projection: KnitProjection, other_projection: KnitProjection,
+                                     clbits=None) -> float:
+        """The Hellinger fidelity ``(sum sqrt(p p'))^2 / (sum p sum p')`` of the two knits' projections (the
+        reference's ``cutVsUncutFidelity`` on what it compares), without either output: one pair pass. ``other``
+        as for :meth:`hellinger_fidelity`; ``projection`` / ``other_projection``: :meth:`project` of this reducer
+        and of ``other`` over the same clbits (``clbits``, when given, must be those) and accuracy. 0.0 when either
+        projection is empty."""
+        st = self._projected_pair_scan(other, projection, other_projection, clbits)
+        return engine.fidelity_from_sums(st["hell"], st["psum"], st["psum2"])
+
+    def projected_total_variation(self, other, projection: KnitProjection, other_projection: KnitProjection,
+                                  clbits=None) -> float:
+        """``sum |p - p'| / 2`` of the two projections (one pair pass; arguments as
+        :meth:`projected_hellinger_fidelity`)."""
+        return self._projected_pair_scan(other, projection, other_projection, clbits)["l1d"] / 2
 
     def marginal_parity(self, clbits, masks):
         """The mixed form: device fp64 ``[M, 2^k]``, row j the marginal onto ``clbits`` of

@@ -685,13 +685,49 @@ def run_virtual_circuit_top_k(virt: VirtualCircuit, k: int, clbits=None, *, capa
 
 
 def run_virtual_circuit_fidelity(virt_a: VirtualCircuit, virt_b: VirtualCircuit, clbits=None, *, device: int = 0,
-                                 factored: bool | None = None, group=None, sample: bool = False):
+                                 factored: bool | None = None, group=None, sample: bool = False, npd: bool = False,
+                                 accuracy: float = 0.0):
     """The Hellinger fidelity of the exact knits of two cut circuits, marginalised onto ``clbits`` (``None`` = all),
     without either 2^N output (:meth:`observables.KnitReducer.hellinger_fidelity`). The circuits must have the same
     number of clbits and, on ``clbits``, fragments that measure the same sets. Returns ``(float, RunTimeInfo)``; both
-    sweeps are ``run_time``. Same restrictions as :func:`run_virtual_circuit_marginal`."""
+    sweeps are ``run_time``. Same restrictions as :func:`run_virtual_circuit_marginal`.
+
+    ``npd=True``: the fidelity of the two knits' nearest probability distributions, each of its entries with
+    ``|R| > accuracy`` (:meth:`observables.KnitReducer.project`, then
+    :meth:`~observables.KnitReducer.projected_hellinger_fidelity`): what the reference's ``cutVsUncutFidelity``
+    compares. The default compares the knits clipped at zero, and ``accuracy`` is then not used."""
     red_a, time_a = _reducer(virt_a, device, factored, group, sample)
     red_b, time_b = _reducer(virt_b, device, factored, group, sample)
     now = perf_counter()
-    value = red_a.hellinger_fidelity(red_b, clbits)
+    if npd:
+        pa, pb = red_a.project(clbits, accuracy=accuracy), red_b.project(clbits, accuracy=accuracy)
+        value = red_a.projected_hellinger_fidelity(red_b, pa, pb)
+    else:
+        value = red_a.hellinger_fidelity(red_b, clbits)
     return value, RunTimeInfo(time_a + time_b, perf_counter() - now)
+
+
+def run_virtual_circuit_npd(virt: VirtualCircuit, *, accuracy: float = _qd.ACCURACY, clbits=None,
+                            capacity: int = 1 << 24, readout=None, mitigate: bool = False, device: int = 0,
+                            factored: bool | None = None):
+    """The reference-shaped result at any output width: ``({key: value}, RunTimeInfo)``, the
+    ``nearest_probability_distribution`` of the knit's entries with ``|R| > accuracy`` (of its marginal onto
+    ``clbits``; of the knit under ``readout`` / ``mitigate`` as in :func:`run_virtual_circuit_marginal`), in ascending
+    order of value, equal values by key: the order of the reference's dict. The 2^N output is never formed: the
+    threshold takes a few passes of ``qk_knit_project_scan`` (:meth:`observables.KnitReducer.project`), the kept
+    entries are collected above it. ``accuracy=0`` projects the whole knit. More than ``capacity`` kept entries
+    raise ``ValueError`` naming the count.
+
+    An entry exactly at the threshold projects to 0.0: the reference lists it with the value 0.0, here it is not
+    listed. One GPU, exact instances, every fragment on the MI355X backend."""
+    red, run_time = _reducer(virt, device, factored, None, False, readout=readout, mitigate=mitigate)
+    now = perf_counter()
+    T = engine.torch()
+    projection = red.project(clbits, accuracy=accuracy)
+    if projection.kept > capacity:
+        raise ValueError(f"{projection.kept} entries in the projection, more than capacity = {capacity}")
+    keys, vals = red.projected_heavy_outputs(projection, capacity=capacity)
+    keys, by_key = T.sort(keys)
+    vals, by_val = T.sort(vals[by_key], stable=True)  # ascending; equal values stay in key order
+    info = RunTimeInfo(run_time, perf_counter() - now)
+    return dict(zip(keys[by_val].tolist(), vals.tolist())), info

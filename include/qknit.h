@@ -641,6 +641,48 @@ int qk_knit_collect(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int
                     int64_t ldb, int64_t i_begin, int64_t i_end, double tau, int64_t capacity, int64_t* idx,
                     double* vals, int64_t* count_dev);
 
+/* ---- nearest probability distribution of the knit (qknit_scan.hip): one pass of the threshold iteration ----
+ * The same operands, tiles, slabs and mainloop as qk_knit_scan. With v an output of the knit, theta >= 0 and
+ * accuracy >= 0 (neither NaN): member = |v| > accuracy, kept = v > max(theta, accuracy) (strict),
+ * p = kept ? v - theta : 0. K2 > 0 adds a second knit v' with its own theta2 (and the same accuracy): p'.
+ * stats[QK_PROJ_NSTATS] doubles: MSUM = sum of v over members, TSUM = sum of v over kept (not shifted),
+ *   PSUM = sum p, PSQ = sum p^2, PENT = sum -p ln p (only with QK_PROJ_ENTROPY in flags, else 0.0), PMAX = max p
+ *   (0.0 where nothing is kept); with K2 > 0 (else 0.0) the same six of p' (MSUM2 ... PMAX2) and
+ *   HELL = sum sqrt(p p'), L1D = sum |p - p'|, MAXD = max |p - p'|.
+ * counts[QK_PROJ_NCOUNTS] int64: NMEMBER, NKEPT, with K2 > 0 NMEMBER2, NKEPT2 (else 0), ARGMAX = the flat index
+ *   of PMAX, the lowest index among equal values.
+ * `work`: qk_knit_project_scan_workspace_bytes(ma, mb, i_begin, i_end) bytes. The association of every sum is
+ * that of qk_knit_scan (thread in tile order, workgroup halving tree, workgroups ascending); the counts are
+ * integer atomics. Two launches give identical bytes. */
+#define QK_PROJ_MSUM 0
+#define QK_PROJ_TSUM 1
+#define QK_PROJ_PSUM 2
+#define QK_PROJ_PSQ 3
+#define QK_PROJ_PENT 4
+#define QK_PROJ_PMAX 5
+#define QK_PROJ_MSUM2 6
+#define QK_PROJ_TSUM2 7
+#define QK_PROJ_PSUM2 8
+#define QK_PROJ_PSQ2 9
+#define QK_PROJ_PENT2 10
+#define QK_PROJ_PMAX2 11
+#define QK_PROJ_HELL 12
+#define QK_PROJ_L1D 13
+#define QK_PROJ_MAXD 14
+#define QK_PROJ_NSTATS 16
+#define QK_PROJ_NMEMBER 0
+#define QK_PROJ_NKEPT 1
+#define QK_PROJ_NMEMBER2 2
+#define QK_PROJ_NKEPT2 3
+#define QK_PROJ_ARGMAX 4
+#define QK_PROJ_NCOUNTS 5
+#define QK_PROJ_ENTROPY 1 /* flags */
+int qk_knit_project_scan_workspace_bytes(int ma, int mb, int64_t i_begin, int64_t i_end, int64_t* bytes);
+int qk_knit_project_scan(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int64_t lda, const double* B,
+                         int64_t ldb, int64_t K2, const double* A2, int64_t lda2, const double* B2, int64_t ldb2,
+                         int64_t i_begin, int64_t i_end, int flags, double theta, double theta2, double accuracy,
+                         double* stats, int64_t* counts, void* work, int64_t work_bytes);
+
 int qk_hellinger(qk_ctx* ctx, int64_t n, const double* p, const double* q, double* acc3);
 
 #ifdef __cplusplus

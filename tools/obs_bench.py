@@ -30,7 +30,10 @@ moments_leg.
 ``--scan`` runs the streamed-scan leg instead (``--out``: e.g. profiles/obs_bench_scan.json): see scan_leg.
 
 ``--channels`` runs the per-clbit channels leg instead (``--out``: e.g. profiles/obs_bench_channels.json): see
-channels_leg."""
+channels_leg.
+
+``--projection`` runs the nearest-probability-distribution leg instead (``--out``: e.g.
+profiles/obs_bench_projection.json): see projection_leg."""
 import argparse
 import glob
 import json
@@ -558,8 +561,125 @@ def channels_leg(args):
             fh.write("\n")
 
 
+def projection_leg(args):
+    """Nearest probability distribution (``--out``: e.g. profiles/obs_bench_projection.json) on syc 32 5: (a) one
+    qk_knit_project_scan pass beside one qk_knit_scan pass on the same operands, alternating in rounds so that both
+    see the same clocks (per kernel the median of the rounds' medians and their spread), also with the entropy
+    launch and as the pair pass against itself; (b) KnitReducer.project end to end under a 2 % symmetric readout
+    mitigation on every clbit: passes, theta, kept, negativity, and beside it (unless --no-dense) the dense step plus
+    the same iteration in torch on the 2^32 tensor; (c) run_virtual_circuit_npd at the default accuracy beside
+    run_virtual_circuit(dense=False); (d) hwe 36 under the same mitigation: passes, time, peak device memory."""
+    import time
+
+    import numpy as np
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import (VirtualCircuit, cutting, engine,
+                                                                          observables as ob, run_virtual_circuit,
+                                                                          run_virtual_circuit_npd)
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.run import run_virtual_circuit_dense
+
+    res = {"config": "syc_32_5_p2", "device": torch.cuda.get_device_name(0), "rounds": 5, "reps_per_round": 10}
+    _, cut, _ = cutting.config_cut_circuit("syc", 32, 5, 2)
+    virt = VirtualCircuit(cut)
+    base = KnitReducer(virt)
+    conf = ob.readout_matrix(0.02, 0.02)
+    red = base.with_readout_mitigation(conf)
+    ctx = engine.get_context(0)
+    K = res["terms"] = int(red.ops.num_terms)
+    A, B, wa, wb, _, _ = red._scan_operands(list(range(red.N)))
+    res["sides"] = {"bits_a": len(wa), "bits_b": len(wb)}
+    theta = red.project().theta
+    legs = {"qk_knit_scan_plain": lambda: engine.knit_scan(ctx, A, B),
+            "qk_knit_project_scan": lambda: engine.knit_project_scan(ctx, A, B, theta=theta),
+            "qk_knit_project_scan_entropy": lambda: engine.knit_project_scan(ctx, A, B, theta=theta, entropy=True),
+            "qk_knit_scan_pair_with_itself": lambda: engine.knit_scan(ctx, A, B, A, B),
+            "qk_knit_project_scan_pair_with_itself": lambda: engine.knit_project_scan(ctx, A, B, A, B, theta=theta,
+                                                                                     theta2=theta)}
+    rounds = {name: [] for name in legs}
+    for _ in range(res["rounds"]):
+        for name, fn in legs.items():
+            rounds[name].append(timed(torch, fn, reps=res["reps_per_round"])["median_ms"])
+    for name, ms in rounds.items():
+        ms = sorted(ms)
+        res[name] = {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1]}
+        print(name, res[name], flush=True)
+    res["project_pass_over_scan_pass"] = res["qk_knit_project_scan"]["median_ms"] / res["qk_knit_scan_plain"]["median_ms"]
+    res["pair_project_pass_over_pair_scan_pass"] = (res["qk_knit_project_scan_pair_with_itself"]["median_ms"]
+                                                    / res["qk_knit_scan_pair_with_itself"]["median_ms"])
+    # (b)
+    pr = red.project()
+    res["project"] = dict(timed(torch, lambda: red.project(), reps=10), passes=pr.passes, theta=pr.theta, kept=pr.kept,
+                          members=pr.members, mass=pr.mass, dropped_mass=pr.dropped_mass,
+                          negativity=red.negativity())
+    print("project", res["project"], flush=True)
+    res["projected_scan_entropy"] = timed(torch, lambda: red.projected_scan(pr), reps=10)
+    # (c)
+    now = time.perf_counter()
+    got, _ = run_virtual_circuit_npd(virt)
+    res["run_virtual_circuit_npd"] = {"seconds": time.perf_counter() - now, "entries": len(got)}
+    now = time.perf_counter()
+    want, _ = run_virtual_circuit(virt, dense=False)
+    res["run_virtual_circuit_dict"] = {"seconds": time.perf_counter() - now, "entries": len(want)}
+    res["npd_vs_dict"] = {"same_keys_in_order": list(got) == list(want),
+                          "max_abs_diff": max((abs(got[k] - want[k]) for k in want if k in got), default=0.0)}
+    print({k: res[k] for k in ("run_virtual_circuit_npd", "run_virtual_circuit_dict", "npd_vs_dict")}, flush=True)
+    # (d), before the dense comparator takes its 100 GB
+    torch.cuda.empty_cache()
+    _, cut, _ = cutting.config_cut_circuit("hwe", 36, 1, 2)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    wide = KnitReducer(VirtualCircuit(cut)).with_readout_mitigation(conf)
+    now = time.perf_counter()
+    pw = wide.project()
+    res["hwe_36_project"] = {"seconds": time.perf_counter() - now, "passes": pw.passes, "theta": pw.theta, "kept": pw.kept,
+                             "members": pw.members, "dropped_mass": pw.dropped_mass,
+                             "peak_device_MiB": torch.cuda.max_memory_allocated() / 2 ** 20}
+    del wide
+    torch.cuda.empty_cache()
+    if args.out:  # what is measured so far, should the comparator run out of memory
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+    if not args.no_dense and red.N == 32 and len(red._measured()) == 32:
+        del A, B
+        torch.cuda.empty_cache()
+        inv = ob.invert_channels(ob.bit_channels(conf, 32, red._measured()))
+        top = torch.from_numpy(np.kron(inv[31], inv[30])).cuda()  # the two bits beyond qk_kron2_rows' 30
+
+        def dense_project():
+            full, _ = run_virtual_circuit_dense(virt)
+            full = full.view(4, -1)
+            engine.kron2_rows(ctx, full, inv[:30], 30, out=full)
+            full = (top @ full).view(-1)
+            m, th, last = float(full.sum()), 0.0, None
+            zero = torch.zeros((), dtype=full.dtype, device=full.device)
+            for passes in range(1, 33):
+                kept = full > th
+                n = int(kept.sum())
+                if n == last:
+                    break
+                th, last = (float(torch.where(kept, full, zero).sum()) - m) / n, n  # a mask index stops at 2^31
+            return th, n, passes
+
+        th, n, passes = dense_project()
+        res["dense_project"] = dict(timed(torch, dense_project, reps=3, warm=0), theta=th, kept=n, passes=passes,
+                                    theta_abs_diff=abs(th - pr.theta), kept_diff=n - pr.kept)
+        print("dense_project", res["dense_project"], flush=True)
+    print(json.dumps(res, indent=1), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--projection", action="store_true",
+                    help="the nearest-probability-distribution leg only (see projection_leg)")
     ap.add_argument("--channels", action="store_true", help="the per-clbit channels leg only (see channels_leg)")
     ap.add_argument("--scan", action="store_true", help="the streamed-scan leg only (see scan_leg)")
     ap.add_argument("--moments", action="store_true", help="the second-moments leg only (see moments_leg)")
@@ -582,6 +702,8 @@ def main():
         return moments_leg(args)
     if args.scan:
         return scan_leg(args)
+    if args.projection:
+        return projection_leg(args)
     if args.channels:
         return channels_leg(args)
     import torch
