@@ -160,6 +160,11 @@ SIGNATURES = {
     "qk_knit_project_scan": (c_i32, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                                      c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                      ctypes.c_double, c_vp, c_vp, c_vp, c_i64]),
+    "qk_knit_project_tiles": (c_i32, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "qk_knit_project_draw_workspace_bytes": (c_i32, [ctypes.c_int, ctypes.c_int, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "qk_knit_project_draw": (c_i32, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                     ctypes.c_double, ctypes.c_double, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
 }
 
 _lock = threading.Lock()

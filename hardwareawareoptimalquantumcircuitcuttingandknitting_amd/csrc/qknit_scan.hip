@@ -9,6 +9,9 @@
 //   qk_knit_project_scan  the same mainloop; one pass of the nearest-probability-distribution iteration: sums and
 //                     counts of the members (|R| > accuracy) and of the kept (R > max(theta, accuracy)), and the
 //                     statistics of p = R - theta on the kept; with a second knit also of p' and of the pair.
+//   qk_knit_project_tiles  the same mainloop; per tile the mass of p, signed by up to 8 Z masks.
+//   qk_knit_project_draw   inverse-CDF draws from p in (tile, walk) order: a prefix over the tile masses, then the
+//                     mainloop again on the one tile that a draw falls into.
 //
 // Layout. A workgroup of 256 threads forms one 128 x 128 tile of R: 2 x 2 waves of 64 x 64 = 4 x 4
 // v_mfma_f64_16x16x4_f64 blocks each, K streamed in chunks of 16 rows through a double-buffered LDS stage
@@ -601,6 +604,279 @@ __global__ __launch_bounds__(SC_THREADS) void knit_project_stage2(int64_t G, con
 
 int64_t pj_work_bytes(const sc_shape& sh) { return sh.groups * (PJ_SLOTS + 1) * 8; }
 
+// ---- the projection as a distribution ("The projection as a distribution"): signed tile masses of
+// p and inverse-CDF draws from it, in (tile, walk) order. The walk order of a tile: thread tid ascending, within a
+// thread block row i, block column j, register r ascending (the outputs sc_row(m0, i, r), sc_col(n0, j)).
+// Association: a thread adds its 64 p in walk order from +0.0; the 256 thread sums are chained serially in tid
+// order from +0.0 (b <- b + sum[tid]). The sums wait for the chain in the LDS stage that the mainloop writes next
+// (every read of it precedes the last chunk's barrier); `buf` is then flipped, so that the next tile's first store
+// goes to the other stage, whose reads precede the barrier before the chain. One barrier per tile, no LDS beyond
+// the mainloop's.
+constexpr int PT_MASKS = QK_PROJ_TILE_MASKS;
+constexpr int PD_MAX_GROUPS = 4096;
+constexpr int PD_SPT = 8;  // tiles per thread and chunk of the prefix
+static_assert(sizeof(double) * SC_K * SC_PITCH >= sizeof(double) * PT_MASKS * SC_THREADS, "the sums alias one stage");
+
+struct TileArgs {
+    int K;
+    const double* __restrict__ A;
+    int64_t lda;
+    const double* __restrict__ B;
+    int64_t ldb;
+    int64_t i_begin, i_end, N;
+    int mb;
+    sc_shape sh;
+    double theta, lower;  // lower = max(theta, accuracy)
+    int n_masks;
+    uint32_t za[PT_MASKS], zb[PT_MASKS];
+    double* __restrict__ W;  // [n_masks][tiles]
+    // draw
+    const double* __restrict__ pre;  // [tiles]: inclusive prefix of the plain tile masses
+    const double* __restrict__ total;
+    int64_t n_draws;
+    const double* __restrict__ u;
+    int64_t* __restrict__ flat;
+    double* __restrict__ pval;
+};
+
+// W[m][t] for m < n_masks <= NM; the masks from n_masks on are (0, 0) and are not stored.
+template <int NM>
+__global__ __launch_bounds__(SC_THREADS, 2) void knit_project_tiles_kernel(TileArgs a) {
+    __shared__ __attribute__((aligned(16))) double As[2][SC_K][SC_PITCH];
+    __shared__ __attribute__((aligned(16))) double Bs[2][SC_K][SC_PITCH];
+    const int tid = threadIdx.x;
+    int buf = 0;
+    for (int64_t t = blockIdx.x; t < a.sh.tiles; t += gridDim.x) {
+        const int64_t m0 = a.i_begin + (t / a.sh.tiles_n) * SC_T, n0 = (t % a.sh.tiles_n) * SC_T;
+        sc_d4 acc[4][4];
+        sc_tile(a.A, a.lda, a.B, a.ldb, a.K, m0, a.i_end, n0, a.N, acc, As, Bs, buf);
+        // The epilogue's thread index, opaque to the compiler: what it derives from it is formed here, per tile, and
+        // does not wait in registers while the mainloop runs.
+        int tq = tid;
+        asm volatile("" : "+v"(tq));
+        // The outputs become their p where they are: no second set of 64 values is ever live. Rows at or past
+        // i_end and columns at or past N hold exact zeros (their operands are zero-filled) and lower >= 0: they are
+        // never kept.
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double v = acc[i][j][r];
+                    acc[i][j][r] = v > a.lower ? v - a.theta : 0.0;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        double(*red)[SC_THREADS] = reinterpret_cast<double(*)[SC_THREADS]>(&As[buf][0][0]);
+        const uint32_t row0 = (uint32_t)m0 + ((tq >> 6) & 1) * 64 + ((tq >> 4) & 3);  // sc_row(m0, i, r) = row0 + 16 i + 4 r
+        const uint32_t col0 = (uint32_t)n0 + (tq >> 7) * 64 + (tq & 15);              // sc_col(n0, j) = col0 + 16 j
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {  // one mask at a time
+            // bit 4 i + r of rpar: the parity of this thread's row (i, r) under za[m]; bit j of cpar: of its column j
+            // under zb[m]
+            uint32_t rpar = 0, cpar = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    rpar |= (uint32_t)(__popc((row0 + 16 * i + 4 * r) & a.za[m]) & 1) << (4 * i + r);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cpar |= (uint32_t)(__popc((col0 + 16 * j) & a.zb[m]) & 1) << j;
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const double p = acc[i][j][r];  // its sign bit flipped where the parity is odd
+                        const uint32_t odd = ((rpar >> (4 * i + r)) ^ (cpar >> j)) << 31;
+                        s += __hiloint2double(__double2hiint(p) ^ (int)odd, __double2loint(p));
+                    }
+            red[m][tq] = s;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+        if (tid < NM && tid < a.n_masks) {
+            double b = 0.0;
+            for (int th = 0; th < SC_THREADS; ++th) b += red[tid][th];
+            a.W[(int64_t)tid * a.sh.tiles + t] = b;
+        }
+        buf ^= 1;
+    }
+}
+
+// pre[t] = the inclusive prefix of W[0..t], total = pre[tiles - 1]: sr_tile_scan's serial chain (qknit_shots.hip),
+// out of place. Monotone where W >= 0 and flat over empty tiles, which the binary search of the draws needs.
+__global__ __launch_bounds__(SC_THREADS) void knit_project_prefix_kernel(int64_t n_tiles, const double* __restrict__ W,
+                                                                         double* __restrict__ pre,
+                                                                         double* __restrict__ total) {
+    __shared__ double part[SC_THREADS];
+    __shared__ double carry_s;
+    const int tid = threadIdx.x;
+    if (tid == 0) carry_s = 0.0;
+    __syncthreads();
+    for (int64_t base = 0; base < n_tiles; base += (int64_t)SC_THREADS * PD_SPT) {
+        double v[PD_SPT];
+        double run = 0.0;
+#pragma unroll
+        for (int k = 0; k < PD_SPT; ++k) {
+            const int64_t i = base + (int64_t)tid * PD_SPT + k;
+            run += i < n_tiles ? W[i] : 0.0;
+            v[k] = run;
+        }
+        part[tid] = run;
+        __syncthreads();
+        if (tid == 0) {  // the thread totals chained serially: part[t] becomes the prefix before thread t
+            const int64_t left = (n_tiles - base + PD_SPT - 1) / PD_SPT;
+            const int used = (int)(left < SC_THREADS ? left : SC_THREADS);
+            double b = carry_s;
+            for (int th = 0; th < used; ++th) {
+                const double tot = part[th];
+                part[th] = b;
+                b += tot;
+            }
+            carry_s = b;
+        }
+        __syncthreads();
+        const double b = part[tid];
+#pragma unroll
+        for (int k = 0; k < PD_SPT; ++k) {
+            const int64_t i = base + (int64_t)tid * PD_SPT + k;
+            if (i < n_tiles) pre[i] = b + v[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) *total = carry_s;  // bit for bit the last prefix
+}
+
+// A value that is the same in every lane but was formed by vector instructions, back in scalar registers.
+__device__ __forceinline__ int64_t pd_uniform(int64_t x) {
+    return ((int64_t)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+}
+__device__ __forceinline__ double pd_uniform(double x) { return __longlong_as_double(pd_uniform((int64_t)__double_as_longlong(x))); }
+
+// One workgroup per draw, grid-stride: the first tile whose prefix exceeds u * total, that tile again (sc_tile: the
+// bits of the tiles kernel), the threads' sums and their exclusive chain, and the first kept output in walk order
+// whose prefix before + (chain + running sum) exceeds the target; if rounding leaves none, the tile's last kept one.
+// One workgroup per CU, as the pair kernels: the two walks beside the mainloop's addresses do not fit the 256 registers
+// that two would leave each wave.
+__global__ __launch_bounds__(SC_THREADS, 1) void knit_project_draw_kernel(TileArgs a) {
+    __shared__ __attribute__((aligned(16))) double As[2][SC_K][SC_PITCH];
+    __shared__ __attribute__((aligned(16))) double Bs[2][SC_K][SC_PITCH];
+    __shared__ int first_s[SC_THREADS / 64], last_s[SC_THREADS / 64];
+    constexpr int NONE = 1 << 30;
+    const int tid = threadIdx.x;
+    const double total = *a.total;
+    if (!(total > 0.0) || total == INFINITY) {  // the whole grid leaves: nothing to draw from
+        for (int64_t d = (int64_t)blockIdx.x * SC_THREADS + tid; d < a.n_draws; d += (int64_t)gridDim.x * SC_THREADS) {
+            a.flat[d] = -1;
+            a.pval[d] = 0.0;
+        }
+        return;
+    }
+    int buf = 0;
+    for (int64_t d = blockIdx.x; d < a.n_draws; d += gridDim.x) {
+        const double target = pd_uniform(a.u[d] * total);
+        int64_t lo = 0, hi = a.sh.tiles - 1;  // the first tile whose inclusive prefix exceeds the target
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (a.pre[mid] > target) hi = mid;
+            else lo = mid + 1;
+        }
+        const int64_t t = pd_uniform(lo);
+        const double before = pd_uniform(t ? a.pre[t - 1] : 0.0);
+        const int64_t m0 = a.i_begin + (t / a.sh.tiles_n) * SC_T, n0 = (t % a.sh.tiles_n) * SC_T;
+        sc_d4 acc[4][4];
+        sc_tile(a.A, a.lda, a.B, a.ldb, a.K, m0, a.i_end, n0, a.N, acc, As, Bs, buf);
+        // the epilogue's thread index, opaque to the compiler as in the tiles kernel
+        int tq = tid;
+        asm volatile("" : "+v"(tq));
+        // The outputs become their p where they are, as in the tiles kernel; a kept output has p > 0 (v > theta
+        // gives v - theta > 0), so the second walk knows the kept by their p.
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double v = acc[i][j][r];
+                    const double p = v > a.lower ? v - a.theta : 0.0;
+                    acc[i][j][r] = p;
+                    s += p;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        double* part = &As[buf][0][0];
+        part[tq] = s;
+        __syncthreads();
+        double ex = 0.0;  // the chain of the tiles kernel, up to this thread
+        for (int th = 0; th < tq; ++th) ex += part[th];
+        int first = NONE, last = -1;  // positions 16 i + 4 j + r of this thread's walk
+        double run = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double p = acc[i][j][r];
+                    run += p;
+                    if (p > 0.0) {
+                        last = 16 * i + 4 * j + r;
+                        if (first == NONE && before + (ex + run) > target) first = 16 * i + 4 * j + r;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        int f = first == NONE ? NONE : 64 * tq + first, l = last < 0 ? -1 : 64 * tq + last;  // walk positions
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int f2 = __shfl_xor(f, off, 64), l2 = __shfl_xor(l, off, 64);
+            f = f2 < f ? f2 : f;
+            l = l2 > l ? l2 : l;
+        }
+        if ((tq & 63) == 0) {
+            first_s[tq >> 6] = f;
+            last_s[tq >> 6] = l;
+        }
+        __syncthreads();
+        f = first_s[0];
+        l = last_s[0];
+#pragma unroll
+        for (int wv = 1; wv < SC_THREADS / 64; ++wv) {
+            f = first_s[wv] < f ? first_s[wv] : f;
+            l = last_s[wv] > l ? last_s[wv] : l;
+        }
+        const int at = f != NONE ? f : l;
+        if (at < 0) {  // a tile without a kept output: only where the prefix is not that of these operands
+            if (tq == 0) {
+                a.flat[d] = -1;
+                a.pval[d] = 0.0;
+            }
+        } else if (tq == (at >> 6)) {
+            // the owner's 64 p through LDS (Bs: past the barriers above nobody reads it), so that the one at a
+            // run-time position is a load, not an indexed register
+            double* mine = &Bs[buf][0][0];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) mine[16 * i + 4 * j + r] = acc[i][j][r];
+            const int i = (at >> 4) & 3, j = (at >> 2) & 3, r = at & 3;
+            const int64_t row = m0 + ((tq >> 6) & 1) * 64 + i * 16 + ((tq >> 4) & 3) + 4 * r;  // sc_row(m0, i, r)
+            const int64_t col = n0 + (tq >> 7) * 64 + j * 16 + (tq & 15);                      // sc_col(n0, j)
+            a.flat[d] = (row << a.mb) | col;
+            a.pval[d] = mine[at & 63];
+        }
+        buf ^= 1;
+    }
+}
+
 int sc_fail(qk_ctx* ctx, const char* msg) {
     if (ctx) ctx->err = msg;
     return QK_EARG;
@@ -787,6 +1063,88 @@ int qk_knit_project_scan(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A
     hipLaunchKernelGGL(knit_project_stage2, dim3(1), block, 0, ctx->stream, sh.groups, a.pstats, a.pidx,
                        pair ? PJ_PAIR : PJ_SINGLE, ent ? 1 : 0, stats, counts);
     return sc_hip(ctx, hipGetLastError(), "knit_project_stage2");
+}
+
+int qk_knit_project_tiles(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int64_t lda, const double* B,
+                          int64_t ldb, int64_t i_begin, int64_t i_end, double theta, double accuracy, int n_masks,
+                          const uint32_t* za, const uint32_t* zb, double* W) {
+    if (!ctx) return QK_EARG;
+    std::string msg;
+    if (const char* bad = sc_check(K, ma, mb, A, lda, B, ldb, i_begin, i_end, 0.0)) {
+        msg = std::string("qk_knit_project_tiles: ") + bad;
+        return sc_fail(ctx, msg.c_str());
+    }
+    if (!(theta >= 0.0) || !(accuracy >= 0.0))  // a NaN fails every comparison
+        return sc_fail(ctx, "qk_knit_project_tiles: theta and accuracy must be numbers >= 0");
+    if (n_masks < 1 || n_masks > PT_MASKS)
+        return sc_fail(ctx, "qk_knit_project_tiles: n_masks must be in 1..QK_PROJ_TILE_MASKS");
+    if (!za || !zb || !W) return sc_fail(ctx, "qk_knit_project_tiles: null masks or W");
+    for (int m = 0; m < n_masks; ++m)
+        if (((uint64_t)za[m] >> ma) || ((uint64_t)zb[m] >> mb))
+            return sc_fail(ctx, "qk_knit_project_tiles: a mask has a bit at or above ma (za) or mb (zb)");
+    int rc = sc_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (rc) return rc;
+    TileArgs a{};
+    a.K = (int)K; a.A = A; a.lda = lda; a.B = B; a.ldb = ldb;
+    a.i_begin = i_begin; a.i_end = i_end; a.N = (int64_t)1 << mb; a.mb = mb;
+    a.sh = sc_make_shape(mb, i_begin, i_end);
+    a.theta = theta; a.lower = theta > accuracy ? theta : accuracy;
+    a.n_masks = n_masks;
+    for (int m = 0; m < n_masks; ++m) {
+        a.za[m] = za[m];
+        a.zb[m] = zb[m];
+    }
+    a.W = W;
+    const dim3 grid((unsigned)a.sh.groups), block(SC_THREADS);
+    if (n_masks == 1) hipLaunchKernelGGL(knit_project_tiles_kernel<1>, grid, block, 0, ctx->stream, a);
+    else if (n_masks == 2) hipLaunchKernelGGL(knit_project_tiles_kernel<2>, grid, block, 0, ctx->stream, a);
+    else if (n_masks <= 4) hipLaunchKernelGGL(knit_project_tiles_kernel<4>, grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL(knit_project_tiles_kernel<PT_MASKS>, grid, block, 0, ctx->stream, a);
+    return sc_hip(ctx, hipGetLastError(), "knit_project_tiles_kernel");
+}
+
+int qk_knit_project_draw_workspace_bytes(int ma, int mb, int64_t i_begin, int64_t i_end, int64_t* bytes) {
+    if (!bytes || ma < 0 || ma > 30 || mb < 0 || mb > 30 || i_begin < 0 || i_begin >= i_end ||
+        i_end > ((int64_t)1 << ma))
+        return QK_EARG;
+    *bytes = sc_make_shape(mb, i_begin, i_end).tiles * (int64_t)sizeof(double);
+    return QK_OK;
+}
+
+int qk_knit_project_draw(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int64_t lda, const double* B,
+                         int64_t ldb, int64_t i_begin, int64_t i_end, double theta, double accuracy, const double* W,
+                         int64_t n_draws, const double* u, int64_t* flat, double* pval, double* total, void* work,
+                         int64_t work_bytes) {
+    if (!ctx) return QK_EARG;
+    std::string msg;
+    if (const char* bad = sc_check(K, ma, mb, A, lda, B, ldb, i_begin, i_end, 0.0)) {
+        msg = std::string("qk_knit_project_draw: ") + bad;
+        return sc_fail(ctx, msg.c_str());
+    }
+    if (!(theta >= 0.0) || !(accuracy >= 0.0))  // a NaN fails every comparison
+        return sc_fail(ctx, "qk_knit_project_draw: theta and accuracy must be numbers >= 0");
+    if (n_draws < 0) return sc_fail(ctx, "qk_knit_project_draw: n_draws must not be negative");
+    if (!W || !total || (n_draws && (!u || !flat || !pval)))
+        return sc_fail(ctx, "qk_knit_project_draw: null W, total or draw buffer");
+    const sc_shape sh = sc_make_shape(mb, i_begin, i_end);
+    if (!work || work_bytes < sh.tiles * (int64_t)sizeof(double))
+        return sc_fail(ctx, "qk_knit_project_draw: workspace too small (qk_knit_project_draw_workspace_bytes)");
+    int rc = sc_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (rc) return rc;
+    double* pre = static_cast<double*>(work);
+    const dim3 block(SC_THREADS);
+    hipLaunchKernelGGL(knit_project_prefix_kernel, dim3(1), block, 0, ctx->stream, sh.tiles, W, pre, total);
+    rc = sc_hip(ctx, hipGetLastError(), "knit_project_prefix_kernel");
+    if (rc || n_draws == 0) return rc;
+    TileArgs a{};
+    a.K = (int)K; a.A = A; a.lda = lda; a.B = B; a.ldb = ldb;
+    a.i_begin = i_begin; a.i_end = i_end; a.N = (int64_t)1 << mb; a.mb = mb;
+    a.sh = sh;
+    a.theta = theta; a.lower = theta > accuracy ? theta : accuracy;
+    a.pre = pre; a.total = total; a.n_draws = n_draws; a.u = u; a.flat = flat; a.pval = pval;
+    const int64_t groups = n_draws < PD_MAX_GROUPS ? n_draws : PD_MAX_GROUPS;
+    hipLaunchKernelGGL(knit_project_draw_kernel, dim3((unsigned)groups), block, 0, ctx->stream, a);
+    return sc_hip(ctx, hipGetLastError(), "knit_project_draw_kernel");
 }
 
 }  // extern "C"

@@ -1088,6 +1088,77 @@ def knit_project_scan(ctx: Context, A, B, A2=None, B2=None, *, theta: float = 0.
     return out
 
 
+PROJ_TILE_MASKS = 8  # QK_PROJ_TILE_MASKS
+
+
+def _project_range(A, B, i_begin, i_end) -> tuple:
+    """``(K, ma, lda, mb, ldb, i_begin, i_end, tiles)`` of a tiles / draw call on ``[i_begin, i_end)``."""
+    K, ma, lda = _scan_side("A", A)
+    _, mb, ldb = _scan_side("B", B, K)
+    if B.device != A.device:
+        raise ValueError("A and B must be on one device")
+    i_begin, i_end = int(i_begin), (1 << ma if i_end is None else int(i_end))
+    if not 0 <= i_begin < i_end <= 1 << ma:
+        raise ValueError(f"need 0 <= i_begin < i_end <= 2^{ma}, not [{i_begin}, {i_end})")
+    tiles = -(-(i_end - i_begin) // 128) * -(-(1 << mb) // 128)
+    return K, ma, lda, mb, ldb, i_begin, i_end, tiles
+
+
+def knit_project_tiles(ctx: Context, A, B, theta: float, accuracy: float, masks=((0, 0),), i_begin: int = 0,
+                       i_end: int | None = None):
+    """``qk_knit_project_tiles``: device float64 ``W [len(masks), tiles]``, per 128 x 128 tile of the rows
+    ``[i_begin, i_end)`` (``observables.scan_shape``; tile ``t = (t // tiles_n, t % tiles_n)``) the sum of
+    ``(-1)^(popcount(i & za) + popcount(j & zb)) p(i, j)`` over its outputs, ``p`` the projection of
+    :func:`knit_project_scan` (``theta`` may be ``inf``: nothing is kept) and ``masks`` one to ``PROJ_TILE_MASKS``
+    pairs ``(za, zb)`` over the absolute side indices. Operands as :func:`knit_scan`, only read. The association is
+    fixed (``observables.project_tile_walk``): two calls give identical bytes."""
+    T = torch()
+    K, ma, lda, mb, ldb, i_begin, i_end, tiles = _project_range(A, B, i_begin, i_end)
+    theta, _, accuracy = check_projection_args(theta, 0.0, accuracy)
+    masks = [(int(za), int(zb)) for za, zb in masks]
+    if not 1 <= len(masks) <= PROJ_TILE_MASKS:
+        raise ValueError(f"{len(masks)} masks: one launch takes 1..{PROJ_TILE_MASKS}")
+    for za, zb in masks:
+        if za < 0 or zb < 0 or za >> ma or zb >> mb:
+            raise ValueError(f"mask ({za:#x}, {zb:#x}) has a bit outside the sides' {ma} and {mb} bits")
+    za = (ctypes.c_uint32 * len(masks))(*[m[0] for m in masks])
+    zb = (ctypes.c_uint32 * len(masks))(*[m[1] for m in masks])
+    W = T.empty((len(masks), tiles), dtype=T.float64, device=A.device)
+    ctx.check(ctx.lib.qk_knit_project_tiles(ctx.handle, K, ma, mb, A.data_ptr(), lda, B.data_ptr(), ldb, i_begin, i_end,
+                                            theta, accuracy, len(masks), za, zb, W.data_ptr()), "qk_knit_project_tiles")
+    return W
+
+
+def knit_project_draw(ctx: Context, A, B, theta: float, accuracy: float, W, u, i_begin: int = 0,
+                      i_end: int | None = None):
+    """``qk_knit_project_draw``: inverse-CDF draws from the projection ``p`` of the rows ``[i_begin, i_end)`` in
+    (tile, walk) order (``observables.project_draw_host`` is the model). ``W``: device float64 ``[tiles]``, the plain
+    tile masses (:func:`knit_project_tiles` with the mask ``(0, 0)`` of the same arguments); ``u``: device float64
+    ``[n_draws]`` in [0, 1). Both only read. Returns ``(flat, pval, total)``: device int64 ``[n_draws]`` flat indices
+    ``i << mb | j`` (absolute; -1 where the total is not > 0), float64 ``[n_draws]`` their ``p``, and the Python
+    float ``total``, the last value of the serial prefix over ``W``."""
+    T = torch()
+    K, ma, lda, mb, ldb, i_begin, i_end, tiles = _project_range(A, B, i_begin, i_end)
+    theta, _, accuracy = check_projection_args(theta, 0.0, accuracy)
+    for name, X, n in (("W", W, tiles), ("u", u, None)):
+        if X.dim() != 1 or X.dtype != T.float64 or X.device != A.device or not X.is_contiguous() or (
+                n is not None and X.numel() != n):
+            raise ValueError(f"{name} must be a contiguous device float64 vector" + (f" of {n} tiles" if n else ""))
+    n = u.numel()
+    flat = T.empty(n, dtype=T.int64, device=A.device)
+    pval = T.empty(n, dtype=T.float64, device=A.device)
+    total = T.empty(1, dtype=T.float64, device=A.device)
+    need = ctypes.c_int64()
+    ctx.check(ctx.lib.qk_knit_project_draw_workspace_bytes(ma, mb, i_begin, i_end, ctypes.byref(need)),
+              "qk_knit_project_draw_workspace_bytes")
+    work = T.empty(need.value // 8, dtype=T.float64, device=A.device)
+    ctx.check(ctx.lib.qk_knit_project_draw(ctx.handle, K, ma, mb, A.data_ptr(), lda, B.data_ptr(), ldb, i_begin, i_end,
+                                           theta, accuracy, W.data_ptr(), n, _ptr(u) if n else None,
+                                           _ptr(flat) if n else None, _ptr(pval) if n else None, total.data_ptr(),
+                                           work.data_ptr(), need.value), "qk_knit_project_draw")
+    return flat, pval, float(total[0])
+
+
 # ----------------------------------------------------------------------------- shot sampling
 _SEED_STRIDE = 0x632BE59BD9B4E019  # per-fragment stream offset (mirrored by oracle/sampling.py)
 _U64 = (1 << 64) - 1

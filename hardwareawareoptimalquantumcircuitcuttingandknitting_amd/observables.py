@@ -624,6 +624,123 @@ def project_scan_host(Xs: list, Ys: list | None = None, theta: float = 0.0, thet
     return out
 
 
+# ----------------------------------------------------------------------------- the projection as a distribution
+PROJ_TILE_MASKS = engine.PROJ_TILE_MASKS
+PROJ_TILE_BYTES = 64 << 20  # the tile masses W [masks, tiles] float64 of one pass: beyond it, fewer masks per pass
+PROJ_DRAW_LABEL = 1 << 20   # the uniforms' label of KnitReducer.projected_sample, clear of sample()'s fragment labels
+PROJ_MARGINAL_MASK_BITS = 6  # projected_marginal by the mask route: 2^k expectations
+
+
+def project_tile_walk() -> np.ndarray:
+    """int64 ``[16384, 2]``: the (row, column) offsets in a 128 x 128 tile in walk order, the order in which
+    ``qk_knit_project_tiles`` adds a tile's outputs and ``qk_knit_project_draw`` counts them: thread ``tid``
+    ascending, within a thread block row ``i``, block column ``j``, register ``r`` ascending, which is the output at
+    row ``64 (wave & 1) + 16 i + (lane >> 4) + 4 r`` and column ``64 (wave >> 1) + 16 j + (lane & 15)`` with
+    ``lane = tid & 63``, ``wave = tid >> 6`` (qknit_scan.hip: sc_row, sc_col)."""
+    tid, i, j, r = np.meshgrid(np.arange(256), np.arange(4), np.arange(4), np.arange(4), indexing="ij")
+    lane, wave = tid & 63, tid >> 6
+    row = 64 * (wave & 1) + 16 * i + (lane >> 4) + 4 * r
+    col = 64 * (wave >> 1) + 16 * j + (lane & 15)
+    return np.stack([row.reshape(-1), col.reshape(-1)], axis=1).astype(np.int64)
+
+
+def _project_sides(Xs: list) -> tuple:
+    if len(Xs) != 2:
+        raise ValueError("the tile models take the two sides [B, A] (side B in the low bits of the flat index)")
+    nb, na = np.asarray(Xs[0]).shape[1], np.asarray(Xs[1]).shape[1]
+    if na & (na - 1) or nb & (nb - 1):
+        raise ValueError(f"sides of {na} and {nb} columns: not powers of two")
+    return na.bit_length() - 1, nb.bit_length() - 1
+
+
+def _project_tiled(Xs: list, theta: float, accuracy: float, i_begin: int, i_end) -> tuple:
+    """``(P [tiles, 128, 128], shape)``: ``p`` of the rows ``[i_begin, i_end)`` cut into the tiles of
+    :func:`scan_shape`, zero where a tile passes the range."""
+    ma, mb = _project_sides(Xs)
+    sh = scan_shape(ma, mb, i_begin, i_end)
+    p = project_scan_host(Xs, theta=theta, accuracy=accuracy)["values"].reshape(1 << ma, 1 << mb)
+    P = np.zeros((sh["tiles_m"] * 128, sh["tiles_n"] * 128), dtype=np.longdouble)
+    P[:sh["i_end"] - sh["i_begin"], :1 << mb] = p[sh["i_begin"]:sh["i_end"]]
+    P = P.reshape(sh["tiles_m"], 128, sh["tiles_n"], 128).transpose(0, 2, 1, 3).reshape(sh["tiles"], 128, 128)
+    return P, sh, ma, mb
+
+
+def project_tiles_host(Xs: list, theta: float, accuracy: float, masks=((0, 0),), i_begin: int = 0,
+                       i_end: int | None = None) -> np.ndarray:
+    """numpy model of ``qk_knit_project_tiles`` in ``np.longdouble``: ``W [len(masks), tiles]``. ``Xs = [B, A]``,
+    the two sides as :func:`project_scan_host` takes them (side B in the low bits); ``masks``: pairs ``(za, zb)``
+    over the absolute side indices."""
+    P, sh, ma, mb = _project_tiled(Xs, theta, accuracy, i_begin, i_end)
+    tm, tn = np.divmod(np.arange(sh["tiles"]), sh["tiles_n"])
+    rows = (sh["i_begin"] + 128 * tm)[:, None] + np.arange(128)  # [tiles, 128] absolute
+    cols = (128 * tn)[:, None] + np.arange(128)
+    out = np.zeros((len(masks), sh["tiles"]), dtype=np.longdouble)
+    for m, (za, zb) in enumerate(masks):
+        if za < 0 or zb < 0 or za >> ma or zb >> mb:
+            raise ValueError(f"mask ({za:#x}, {zb:#x}) has a bit outside the sides' {ma} and {mb} bits")
+        sa = 1 - 2 * (_popcount(rows & za) & 1)
+        sb = 1 - 2 * (_popcount(cols & zb) & 1)
+        out[m] = (P * sa[:, :, None] * sb[:, None, :]).sum(axis=(1, 2))
+    return out
+
+
+def _popcount(x) -> np.ndarray:
+    x = np.asarray(x, dtype=np.int64)
+    n = np.zeros_like(x)
+    while np.any(x):
+        n += x & 1
+        x = x >> 1
+    return n
+
+
+def project_draw_host(Xs: list, theta: float, accuracy: float, u, i_begin: int = 0, i_end: int | None = None) -> tuple:
+    """numpy model of ``qk_knit_project_draw`` in ``np.longdouble``: ``(flat int64 [n], pval [n], total)`` from the
+    CDF of ``p`` in (tile, walk) order, draw ``d`` being the first output whose inclusive prefix exceeds
+    ``u[d] * total``; ``flat = -1`` and ``pval = 0`` where the total is not > 0. ``Xs`` as
+    :func:`project_tiles_host`."""
+    P, sh, ma, mb = _project_tiled(Xs, theta, accuracy, i_begin, i_end)
+    walk = project_tile_walk()
+    seq = P[:, walk[:, 0], walk[:, 1]].reshape(-1)
+    u = np.asarray(u, dtype=np.longdouble).reshape(-1)
+    cdf = np.cumsum(seq)
+    total = cdf[-1]
+    if not total > 0:
+        return np.full(u.size, -1, dtype=np.int64), np.zeros(u.size, dtype=np.longdouble), total
+    kept = np.flatnonzero(seq > 0)
+    at = np.minimum(np.searchsorted(cdf, u * total, side="right"), kept[-1])
+    at = kept[np.searchsorted(kept, at)]  # an output that is kept: the prefix rises only there
+    tile, pos = np.divmod(at, 16384)
+    row = sh["i_begin"] + 128 * (tile // sh["tiles_n"]) + walk[pos, 0]
+    col = 128 * (tile % sh["tiles_n"]) + walk[pos, 1]
+    return (row << mb | col).astype(np.int64), seq[at], total
+
+
+def project_walk_rank(ma: int, mb: int, i_begin: int = 0, i_end: int | None = None) -> np.ndarray:
+    """int64 ``[2^(ma + mb)]``: the rank of every flat index ``i << mb | j`` in the (tile, walk) order of the rows
+    ``[i_begin, i_end)`` (``16384 tile + position in the walk``); -1 for a row outside the range."""
+    sh = scan_shape(ma, mb, i_begin, i_end)
+    walk = project_tile_walk()
+    pos = np.empty((128, 128), dtype=np.int64)
+    pos[walk[:, 0], walk[:, 1]] = np.arange(16384)
+    i, j = np.arange(sh["i_begin"], sh["i_end"])[:, None], np.arange(1 << mb)[None, :]
+    tile = ((i - sh["i_begin"]) >> 7) * sh["tiles_n"] + (j >> 7)
+    out = np.full((1 << ma, 1 << mb), -1, dtype=np.int64)
+    out[sh["i_begin"]:sh["i_end"]] = 16384 * tile + pos[(i - sh["i_begin"]) & 127, j & 127]
+    return out.reshape(-1)
+
+
+def inverse_wht_marginal(values) -> np.ndarray:
+    """The ``2^k`` entries of a distribution over ``k`` bits from its ``2^k`` Z-string expectation values,
+    ``values[s] = sum_y (-1)^popcount(s & y) q[y]``: ``q[y] = 2^-k sum_s (-1)^popcount(s & y) values[s]``."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    k = v.size.bit_length() - 1
+    if v.size != 1 << k:
+        raise ValueError(f"{v.size} values: not a power of two")
+    s = np.arange(v.size)
+    H = 1 - 2 * (_popcount(s[:, None] & s[None, :]) & 1)
+    return (H @ v) / v.size
+
+
 @dataclass
 class ProjectionThreshold:
     """What :func:`projection_threshold` returns. ``msum`` / ``tsum``: the last evaluation's."""
@@ -1470,6 +1587,149 @@ class KnitReducer:
         """``sum |p - p'| / 2`` of the two projections (one pair pass; arguments as
         :meth:`projected_hellinger_fidelity`)."""
         return self._projected_pair_scan(other, projection, other_projection, clbits)["l1d"] / 2
+
+    # -- the projection as a distribution -------------------------------------------------------
+    def _tile_masses(self, A, B, projection: KnitProjection, pairs: list) -> list:
+        """Per slab of side A the device ``W [len(pairs), tiles]`` of ``qk_knit_project_tiles``."""
+        ma, mb = A.shape[1].bit_length() - 1, B.shape[1].bit_length() - 1
+        return [engine.knit_project_tiles(self.ctx, A, B, projection.theta, projection.accuracy, pairs, i0, i1)
+                for i0, i1 in engine.scan_slabs(ma, mb)]
+
+    def projected_expectation(self, masks, projection: KnitProjection) -> np.ndarray:
+        """float64 ``[M]``: ``sum_key (-1)^popcount(key & mask) p[key]`` of the projection ``p`` (:meth:`project`)
+        per Z string; masks as for :meth:`expectation` (ints, ``'IZ'`` strings, an integer array or tensor) over
+        the circuit's clbits, every bit within ``projection.clbits``. ``p`` is not multilinear in the fragments: each
+        pass forms all its outcomes (``qk_knit_project_tiles``, DESIGN.md §4a "The projection as a distribution")
+        and answers up to ``PROJ_TILE_MASKS`` masks, fewer where the tile masses of a pass would exceed
+        ``PROJ_TILE_BYTES``. A bit on a clbit that no fragment measures is dropped. A mask's tile masses are added as
+        one vector per slab (a fixed association for a given shape), the slabs ascending on the host."""
+        self._check_projection(projection)
+        self.ctx.bind_stream()
+        T = engine.torch()
+        cl = list(projection.clbits)
+        zs = masks_array(masks, self.N)
+        held = sum(1 << c for c in cl)
+        for z in zs:
+            if int(z) & ~held:
+                raise ValueError(f"mask {int(z):#x} has a bit outside the projection's clbits {cl}")
+        out = np.zeros(len(zs))
+        if not len(zs):
+            return out
+        A, B, wa, wb, _, _ = self._scan_operands(cl)
+        side = lambda z, w: sum(1 << i for i, b in enumerate(w) if z >> cl[b] & 1)
+        pairs = [(side(int(z), wa), side(int(z), wb)) for z in zs]
+        ma, mb = len(wa), len(wb)
+        tiles = sum(scan_shape(ma, mb, i0, i1)["tiles"] for i0, i1 in engine.scan_slabs(ma, mb))
+        per = max(1, min(PROJ_TILE_MASKS, PROJ_TILE_BYTES // (8 * tiles)))
+        for c0 in range(0, len(pairs), per):
+            chunk = pairs[c0:c0 + per]
+            sums = [T.stack([W[m].sum() for m in range(len(chunk))]) for W in self._tile_masses(A, B, projection, chunk)]
+            acc = np.zeros(len(chunk))
+            for s in T.stack(sums).cpu().numpy():  # ascending slabs
+                acc = acc + s
+            out[c0:c0 + len(chunk)] = acc
+        return out
+
+    def projected_marginal(self, clbits, projection: KnitProjection, *, route: str | None = None):
+        """Device fp64 ``[2^k]``: the projection summed over every clbit but ``clbits`` (a subset of
+        ``projection.clbits``; bit ``i`` of the index is ``clbits[i]``): the marginal of the nearest probability
+        distribution, not the nearest probability distribution of the marginal (``project(clbits)``).
+        ``route="tile"``: each side's columns are permuted so that its kept bits are the top bits of its index; with
+        at most ``max(side bits - 7, 0)`` kept bits per side every 128 x 128 tile lies in one cell and the marginal
+        is the sum of the plain tile masses per cell: one pass. ``route="mask"``: for ``k <=
+        PROJ_MARGINAL_MASK_BITS``, the ``2^k`` :meth:`projected_expectation` values of the masks inside ``clbits``
+        and their inverse Walsh-Hadamard transform (:func:`inverse_wht_marginal`): ``2^k / 8`` passes. ``None``: the
+        tile route where it applies, else the mask route, else ``ValueError``. The routes agree to rounding."""
+        self._check_projection(projection)
+        self.ctx.bind_stream()
+        T = engine.torch()
+        dev = T.device("cuda", self.device)
+        cl, pcl = check_clbits(clbits, self.N), list(projection.clbits)
+        if set(cl) - set(pcl):
+            raise ValueError(f"clbits {sorted(set(cl) - set(pcl))} are not among the projection's {pcl}")
+        if route not in (None, "tile", "mask"):
+            raise ValueError(f"route must be None, 'tile' or 'mask', not {route!r}")
+        k = len(cl)
+        A, B, wa, wb, _, _ = self._scan_operands(pcl)
+        ma, mb = len(wa), len(wb)
+        want = {pcl.index(c): i for i, c in enumerate(cl)}  # key bit of the projection -> bit of the result
+        ka, kb = [i for i, b in enumerate(wa) if b in want], [i for i, b in enumerate(wb) if b in want]
+        tile_ok = len(ka) <= max(ma - 7, 0) and len(kb) <= max(mb - 7, 0)
+        if route == "tile" and not tile_ok:
+            raise ValueError(f"the tile route keeps at most max(side bits - 7, 0) bits per side: {len(ka)} of {ma} and "
+                             f"{len(kb)} of {mb} here")
+        if route == "mask" and k > PROJ_MARGINAL_MASK_BITS:
+            raise ValueError(f"the mask route takes at most {PROJ_MARGINAL_MASK_BITS} clbits, not {k}")
+        if route is None and not tile_ok and k > PROJ_MARGINAL_MASK_BITS:
+            raise ValueError(f"{k} clbits: the tile route keeps at most max(side bits - 7, 0) bits per side ({len(ka)} "
+                             f"of {ma} and {len(kb)} of {mb} here), the mask route at most {PROJ_MARGINAL_MASK_BITS} "
+                             f"clbits")
+        if route == "mask" or (route is None and not tile_ok):
+            masks = [sum(1 << c for i, c in enumerate(cl) if s >> i & 1) for s in range(1 << k)]
+            return T.from_numpy(inverse_wht_marginal(self.projected_expectation(masks, projection))).to(dev)
+        na, nb = len(ka), len(kb)
+        A = _permute_bits(T, A, [i for i in range(ma) if i not in ka] + ka if na else None)
+        B = _permute_bits(T, B, [i for i in range(mb) if i not in kb] + kb if nb else None)
+        cells = T.zeros((1 << na, 1 << nb), dtype=T.float64, device=dev)
+        gb = max(1, (1 << (mb - nb)) >> 7)  # tile columns per cell
+        for (i0, i1), W in zip(engine.scan_slabs(ma, mb), self._tile_masses(A.contiguous(), B.contiguous(), projection,
+                                                                           [(0, 0)])):
+            tiles_m = -(-(i1 - i0) // 128)
+            ga = min(tiles_m, max(1, (1 << (ma - na)) >> 7))  # tile rows per cell, within this slab
+            first = i0 >> (ma - na)
+            cells[first:first + tiles_m // ga] += W[0].view(tiles_m // ga, ga, 1 << nb, gb).sum(dim=(1, 3))
+        y = T.arange(1 << k, dtype=T.int64, device=dev)
+        ca = extract_bits(y, [want[wa[i]] for i in ka])
+        cb = extract_bits(y, [want[wb[i]] for i in kb])
+        dead = sum(1 << i for b, i in want.items() if b not in wa and b not in wb)  # nobody measures them: zeros
+        return T.where((y & dead) == 0, cells[ca, cb], T.zeros((), dtype=T.float64, device=dev))
+
+    def projected_sample(self, shots: int, projection: KnitProjection, seed: int = 0):
+        """``shots`` outcomes distributed as the projection ``p / sum p``: device int64 ``[shots]`` of keys over
+        ``projection.clbits`` in draw order. Inverse-CDF draws in (tile, walk) order (``qk_knit_project_tiles`` for
+        the tile masses, then ``qk_knit_project_draw``: a draw forms the one tile it falls into again) with
+        ``u = engine.uniforms(seed, PROJ_DRAW_LABEL, 0, shots)``: a pure function of (circuit, projection, seed, shot
+        index), the first ``n`` shots of a longer run being an ``n``-shot run. Every key has ``p > 0``, which
+        :meth:`sample`'s fragment-by-fragment chain does not give for a knit with negative entries.
+        ``RuntimeError`` for an empty projection with ``shots > 0``."""
+        self._check_projection(projection)
+        self.ctx.bind_stream()
+        T = engine.torch()
+        dev = T.device("cuda", self.device)
+        shots = int(shots)
+        if shots < 0:
+            raise ValueError(f"shots must not be negative, not {shots}")
+        if shots == 0:
+            return T.zeros(0, dtype=T.int64, device=dev)
+        cl = list(projection.clbits)
+        A, B, wa, wb, _, _ = self._scan_operands(cl)
+        ma, mb = len(wa), len(wb)
+        slabs = engine.scan_slabs(ma, mb)
+        Ws = [W[0] for W in self._tile_masses(A, B, projection, [(0, 0)])]
+        u = engine.uniforms(self.ctx, seed, PROJ_DRAW_LABEL, 0, shots)
+        draw = lambda s, us: engine.knit_project_draw(self.ctx, A, B, projection.theta, projection.accuracy, Ws[s], us,
+                                                      *slabs[s])
+        if len(slabs) == 1:
+            flat, _, total = draw(0, u)
+            if not total > 0:
+                raise RuntimeError("the projection is empty: nothing to draw from")
+        else:
+            # the slab of a draw from the chain of the slabs' totals, then the draw within it at the rescaled u
+            totals = np.array([draw(s, u[:0])[2] for s in range(len(slabs))])
+            cum = np.cumsum(totals)  # a serial chain, ascending
+            if not cum[-1] > 0:
+                raise RuntimeError("the projection is empty: nothing to draw from")
+            target = u * float(cum[-1])
+            of = T.clamp(T.searchsorted(T.from_numpy(cum).to(dev), target, right=True), max=len(slabs) - 1)
+            flat = T.empty(shots, dtype=T.int64, device=dev)
+            for s in T.unique(of).tolist():
+                sel = T.nonzero(of == s).reshape(-1)
+                before = float(cum[s - 1]) if s else 0.0
+                us = T.clamp((target[sel] - before) / float(totals[s]), 0.0, float(np.nextafter(1.0, 0.0)))
+                flat[sel] = draw(s, us.contiguous())[0]
+        if bool((flat < 0).any()):
+            raise RuntimeError("the projection is empty: nothing to draw from")
+        return self._scan_key(flat, mb, wa, wb)
 
     def marginal_parity(self, clbits, masks):
         """The mixed form: device fp64 ``[M, 2^k]``, row j the marginal onto ``clbits`` of

@@ -521,7 +521,7 @@ def _reducer(virt: VirtualCircuit, device: int, factored, group, sample: bool, *
 
 def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 0, dense: bool = False,
                                  factored: bool | None = None, group=None, sample: bool = False,
-                                 readout=None, mitigate: bool = False):
+                                 readout=None, mitigate: bool = False, npd: bool = False, accuracy: float = 0.0):
     """The knit's distribution of the clbits ``clbits`` alone (bit ``i`` of a key = ``clbits[i]``), all
     others summed out, without the 2^N output: the swept rows are reduced per fragment
     (``qk_reduce_bits``) and knitted narrow (:class:`observables.KnitReducer`). Returns
@@ -538,9 +538,21 @@ def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 
     (``KnitReducer.with_readout_error`` / ``with_readout_mitigation``; the swept rows are transformed once, inside
     ``run_time``). The other single-circuit entry points below take the same two keywords.
 
+    ``npd=True``: the marginal of the nearest probability distribution of the full knit instead (``KnitReducer.project``
+    over all clbits with the truncation ``accuracy``, then ``projected_marginal``): ``dense=True`` the tensor,
+    ``dense=False`` the dict ``{key: value}`` of its positive entries.
+
     One GPU, exact instances, every fragment on the MI355X backend (``ValueError`` otherwise)."""
     red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
+    if npd:
+        out = red.projected_marginal(clbits, red.project(accuracy=accuracy))
+        _sync(device)
+        info = RunTimeInfo(run_time, perf_counter() - now)
+        if dense:
+            return out, info
+        keys = engine.torch().nonzero(out > 0).reshape(-1)
+        return dict(zip(keys.tolist(), out[keys].tolist())), info
     out = red.marginal(clbits)
     if dense:
         _sync(device)
@@ -553,7 +565,8 @@ def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 
 
 def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device: int = 0,
                                     factored: bool | None = None, group=None, sample: bool = False,
-                                    weights=None, method: str = "reduce", readout=None, mitigate: bool = False):
+                                    weights=None, method: str = "reduce", readout=None, mitigate: bool = False,
+                                    npd: bool = False, accuracy: float = 0.0):
     """Expectation values of Pauli-Z strings on the exact knit (the quasi-distribution itself, no
     projection): ``sum_key (-1)^popcount(key & mask) R[key]`` per observable, without the 2^N output.
     ``observables``: int masks over the clbits, or ``'ZIIZ'`` strings (rightmost character = clbit 0,
@@ -565,12 +578,29 @@ def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device
     thousands of strings and more; the masks may then be an integer numpy array or an int64 tensor.
     ``method="fused"`` reads the same spectra with the lookup kernel (``qk_knit_at``), one launch for all masks.
     ``weights`` (one per observable): the result is the float ``sum_j weights[j] <Z_j>`` instead, always
-    by the spectrum route."""
+    by the spectrum route.
+
+    ``npd=True``: of the nearest probability distribution of the knit instead (``KnitReducer.project`` over all clbits
+    with the truncation ``accuracy``, then ``projected_expectation``: passes over all outcomes, eight masks each);
+    the values then lie in [-mass, mass]. ``weights`` gives the weighted sum, formed on the host; ``method`` must be
+    left at its default."""
+    if npd and method != "reduce":
+        raise ValueError(f"npd=True has one route: method must be left at its default, not {method!r}")
     if method not in ("reduce", "spectrum", "fused"):
         raise ValueError(f"method must be 'reduce', 'spectrum' or 'fused', not {method!r}")
     red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
-    vals = red.expectation(observables, method=method) if weights is None else red.expectation_sum(observables, weights)
+    if npd:
+        vals = red.projected_expectation(observables, red.project(accuracy=accuracy))
+        if weights is not None:
+            w = np.asarray(weights.cpu() if hasattr(weights, "cpu") else weights, dtype=np.float64)
+            if w.ndim != 1 or len(w) != len(vals):
+                raise ValueError(f"{len(vals)} masks but weights of shape {w.shape}")
+            vals = float(np.dot(vals, w))
+    elif weights is None:
+        vals = red.expectation(observables, method=method)
+    else:
+        vals = red.expectation_sum(observables, weights)
     info = RunTimeInfo(run_time, perf_counter() - now)
     log.info("Knitted in %.2fs.", info.knit_time)
     return vals, info
@@ -578,7 +608,8 @@ def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device
 
 def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed: int = 0, clbits=None,
                               memory: bool = False, device: int = 0, factored: bool | None = None, group=None,
-                              sample: bool = False, readout=None, mitigate: bool = False):
+                              sample: bool = False, readout=None, mitigate: bool = False, npd: bool = False,
+                              accuracy: float = 0.0):
     """``shots`` measurement outcomes distributed as the exact knit, i.e. as the uncut circuit's output,
     without the 2^N distribution: drawn fragment by fragment from the swept rows
     (:meth:`observables.KnitReducer.sample`, ``qk_sample_rows``). Not ``run_virtual_circuit(sample=True)``,
@@ -588,10 +619,18 @@ def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed:
     ``memory=False``: counts ``{key: count}`` (Python ints); ``memory=True``: the device int64 tensor
     ``[shots]`` of keys in draw order. ``clbits``: the measured clbits (bit ``i`` of a key = ``clbits[i]``),
     ``None`` = all. A pure function of (circuit, ``seed``, ``shots``); the first ``n`` shots of a longer
-    run are an ``n``-shot run. Same restrictions as :func:`run_virtual_circuit_marginal`."""
+    run are an ``n``-shot run. Same restrictions as :func:`run_virtual_circuit_marginal`.
+
+    ``npd=True``: drawn from the nearest probability distribution of the knit instead (``KnitReducer.project`` over
+    ``clbits`` with the truncation ``accuracy``, then ``projected_sample``): what the shots of a knit with negative
+    entries, a readout-mitigated one say, should follow. The fragment-by-fragment chain draws from clipped
+    conditionals, which is exact only for a non-negative knit."""
     red, run_time = _reducer(virt, device, factored, group, sample, readout=readout, mitigate=mitigate)
     now = perf_counter()
-    keys = red.sample(shots, seed, clbits)
+    if npd:
+        keys = red.projected_sample(shots, red.project(clbits, accuracy=accuracy), seed)
+    else:
+        keys = red.sample(shots, seed, clbits)
     if memory:
         _sync(device)
         return keys, RunTimeInfo(run_time, perf_counter() - now)

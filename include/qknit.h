@@ -683,6 +683,33 @@ int qk_knit_project_scan(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A
                          int64_t i_begin, int64_t i_end, int flags, double theta, double theta2, double accuracy,
                          double* stats, int64_t* counts, void* work, int64_t work_bytes);
 
+/* ---- the projection as a distribution (qknit_scan.hip): signed tile masses and inverse-CDF draws ----
+ * Operands, tiles (tile t = (t / tiles_n, t % tiles_n) over [i_begin, i_end), 128 x 128 outputs), theta, accuracy
+ * and p as for qk_knit_project_scan; theta may be +inf (nothing is kept). The walk order of a tile: thread tid
+ * ascending, within a thread block row i, block column j, register r ascending, which is the output at row
+ * m0 + 64 (wave & 1) + 16 i + (lane >> 4) + 4 r and column n0 + 64 (wave >> 1) + 16 j + (lane & 15), with
+ * lane = tid & 63, wave = tid >> 6 (observables.project_tile_walk is the host model).
+ * qk_knit_project_tiles: W[m * tiles + t] = sum over the outputs (i, j) of tile t of
+ *   (-1)^(popcount(i & za[m]) + popcount(j & zb[m])) p(i, j) for m < n_masks (1..QK_PROJ_TILE_MASKS); za / zb are
+ *   host arrays of masks over the absolute side indices (no bit at or above ma / mb). A thread adds its 64 outputs
+ *   in walk order, the 256 thread sums are chained serially in tid order; one store per (m, t), no atomics.
+ * qk_knit_project_draw: `W`: the plain tile masses (mask (0, 0)) of the same arguments, [tiles], only read; `u`:
+ *   n_draws doubles in [0, 1). total[0] = the last value of the serial inclusive prefix of W (kept in `work`,
+ *   qk_knit_project_draw_workspace_bytes). Draw d: target = u[d] * total, the first tile whose prefix exceeds it, and
+ *   in that tile the first kept output in walk order whose prefix (the prefix before the tile + (the chain of the
+ *   earlier threads' sums + the thread's running sum)) exceeds it; if rounding leaves none, the tile's last kept
+ *   output. flat[d] = i << mb | j (absolute), pval[d] = its p; total <= 0: flat[d] = -1, pval[d] = 0.
+ * Two launches give identical bytes; A, B, W, u are only read. */
+#define QK_PROJ_TILE_MASKS 8
+int qk_knit_project_tiles(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int64_t lda, const double* B,
+                          int64_t ldb, int64_t i_begin, int64_t i_end, double theta, double accuracy, int n_masks,
+                          const uint32_t* za, const uint32_t* zb, double* W);
+int qk_knit_project_draw_workspace_bytes(int ma, int mb, int64_t i_begin, int64_t i_end, int64_t* bytes);
+int qk_knit_project_draw(qk_ctx* ctx, int64_t K, int ma, int mb, const double* A, int64_t lda, const double* B,
+                         int64_t ldb, int64_t i_begin, int64_t i_end, double theta, double accuracy, const double* W,
+                         int64_t n_draws, const double* u, int64_t* flat, double* pval, double* total, void* work,
+                         int64_t work_bytes);
+
 int qk_hellinger(qk_ctx* ctx, int64_t n, const double* p, const double* q, double* acc3);
 
 #ifdef __cplusplus

@@ -33,7 +33,8 @@ moments_leg.
 channels_leg.
 
 ``--projection`` runs the nearest-probability-distribution leg instead (``--out``: e.g.
-profiles/obs_bench_projection.json): see projection_leg."""
+profiles/obs_bench_projection.json): see projection_leg. ``--projected`` the projection as a distribution (``--out``:
+profiles/obs_bench_projected.json): see projected_leg."""
 import argparse
 import glob
 import json
@@ -676,10 +677,142 @@ def projection_leg(args):
             fh.write("\n")
 
 
+def projected_leg(args):
+    """The projection as a distribution (``--out``: e.g. profiles/obs_bench_projected.json) on syc 32 5 under the 2 %
+    symmetric readout mitigation of projection_leg: (a) qk_knit_project_tiles with 1 and with 8 masks beside one
+    qk_knit_project_scan pass on the same operands, alternating in rounds (per kernel the median of the rounds' medians
+    and their spread); (b) qk_knit_project_draw for 20000 draws; (c) KnitReducer.projected_sample of 20000 shots and
+    projected_expectation of 8 masks end to end from the swept rows (project included), and beside them (unless
+    --no-dense) the dense step, the same Newton iteration in torch on the 2^32 tensor, then row-wise cumsum +
+    searchsorted (20000 draws) or a signed sum (8 masks)."""
+    import numpy as np
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine, observables as ob
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.run import run_virtual_circuit_dense
+
+    shots = 20000
+    res = {"config": "syc_32_5_p2", "device": torch.cuda.get_device_name(0), "rounds": 5, "reps_per_round": 10,
+           "shots": shots}
+    _, cut, _ = cutting.config_cut_circuit("syc", 32, 5, 2)
+    virt = VirtualCircuit(cut)
+    conf = ob.readout_matrix(0.02, 0.02)
+    red = KnitReducer(virt).with_readout_mitigation(conf)
+    ctx = engine.get_context(0)
+    res["terms"] = K = int(red.ops.num_terms)
+    A, B, wa, wb, _, _ = red._scan_operands(list(range(red.N)))
+    res["sides"] = {"bits_a": len(wa), "bits_b": len(wb)}
+    pr = red.project()
+    theta = pr.theta
+    res["projection"] = {"theta": theta, "kept": pr.kept, "members": pr.members, "passes": pr.passes}
+    rng = random.Random(1)
+    pairs = [(0, 0)] + [(rng.getrandbits(len(wa)), rng.getrandbits(len(wb))) for _ in range(7)]
+    # (a)
+    legs = {"qk_knit_project_scan": lambda: engine.knit_project_scan(ctx, A, B, theta=theta),
+            "qk_knit_project_tiles_1_mask": lambda: engine.knit_project_tiles(ctx, A, B, theta, 0.0, pairs[:1]),
+            "qk_knit_project_tiles_8_masks": lambda: engine.knit_project_tiles(ctx, A, B, theta, 0.0, pairs)}
+    rounds = {name: [] for name in legs}
+    for _ in range(res["rounds"]):
+        for name, fn in legs.items():
+            rounds[name].append(timed(torch, fn, reps=res["reps_per_round"])["median_ms"])
+    for name, ms in rounds.items():
+        ms = sorted(ms)
+        res[name] = {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1]}
+        print(name, res[name], flush=True)
+    scan_ms = res["qk_knit_project_scan"]
+    res["tiles_1_mask_over_project_scan"] = res["qk_knit_project_tiles_1_mask"]["median_ms"] / scan_ms["median_ms"]
+    res["tiles_8_masks_over_project_scan"] = res["qk_knit_project_tiles_8_masks"]["median_ms"] / scan_ms["median_ms"]
+    res["tiles_1_mask_within_1p1_of_the_scan_spread"] = bool(
+        res["qk_knit_project_tiles_1_mask"]["median_ms"] <= 1.1 * scan_ms["max_ms"])
+    # (b)
+    W = engine.knit_project_tiles(ctx, A, B, theta, 0.0)[0].contiguous()
+    u = engine.uniforms(ctx, 0, ob.PROJ_DRAW_LABEL, 0, shots)
+    res["qk_knit_project_draw_20000"] = timed(torch, lambda: engine.knit_project_draw(ctx, A, B, theta, 0.0, W, u), reps=10)
+    res["qk_knit_project_draw_20000"]["GFLOP"] = shots * 2 * 128 * 128 * K / 1e9
+    print("draw", res["qk_knit_project_draw_20000"], flush=True)
+    # (c)
+    masks = [0] + [rng.getrandbits(red.N) for _ in range(7)]
+    res["projected_sample_20000_end_to_end"] = timed(torch, lambda: red.projected_sample(shots, red.project(), 0), reps=10)
+    res["projected_expectation_8_end_to_end"] = timed(torch, lambda: red.projected_expectation(masks, red.project()),
+                                                      reps=10)
+    got_e = red.projected_expectation(masks, pr)
+    keys = red.projected_sample(shots, pr, 0)
+    res["check"] = {"mass": float(got_e[0]), "projection_mass": pr.mass,
+                    "every_shot_in_the_support": bool((red.projected_probabilities(keys, pr) > 0).all())}
+    print({k: res[k] for k in ("projected_sample_20000_end_to_end", "projected_expectation_8_end_to_end", "check")},
+          flush=True)
+    if args.out:  # what is measured so far, should the comparator run out of memory
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+    if not args.no_dense and red.N == 32 and len(red._measured()) == 32:
+        del A, B, W
+        torch.cuda.empty_cache()
+        inv = ob.invert_channels(ob.bit_channels(conf, 32, red._measured()))
+        top = torch.from_numpy(np.kron(inv[31], inv[30])).cuda()  # the two bits beyond qk_kron2_rows' 30
+        lo = torch.arange(1 << 16, device="cuda")
+
+        def dense_projection():
+            full, _ = run_virtual_circuit_dense(virt)
+            full = full.view(4, -1)
+            engine.kron2_rows(ctx, full, inv[:30], 30, out=full)
+            full = (top @ full).view(-1)
+            m, th, last = float(full.sum()), 0.0, None
+            zero = torch.zeros((), dtype=full.dtype, device=full.device)
+            for _ in range(32):
+                kept = full > th
+                n = int(kept.sum())
+                if n == last:
+                    break
+                th, last = (float(torch.where(kept, full, zero).sum()) - m) / n, n
+            return torch.where(full > th, full - th, zero).view(1 << 16, 1 << 16)
+
+        def dense_sample():
+            p = dense_projection()
+            rows = torch.cumsum(p.sum(dim=1), 0)
+            target = engine.uniforms(ctx, 0, ob.PROJ_DRAW_LABEL, 0, shots) * rows[-1]
+            r = torch.clamp(torch.searchsorted(rows, target, right=True), max=(1 << 16) - 1)
+            rest = target - torch.where(r > 0, rows[torch.clamp(r - 1, min=0)], torch.zeros_like(target))
+            out = torch.empty(shots, dtype=torch.int64, device="cuda")
+            for s in range(0, shots, 2000):  # [2000, 2^16] doubles at a time
+                c = torch.cumsum(p[r[s:s + 2000]], dim=1)
+                x = torch.searchsorted(c, rest[s:s + 2000, None], right=True).view(-1)
+                out[s:s + 2000] = (r[s:s + 2000] << 16) | torch.clamp(x, max=(1 << 16) - 1)
+            return out
+
+        def signs(shift):  # [2^16, 8] of +-1: the parity of the masks' 16 bits from `shift` on
+            z = torch.tensor([(v >> shift) & 0xFFFF for v in masks], device="cuda")
+            par = torch.zeros((1 << 16, len(masks)), dtype=torch.int64, device="cuda")
+            for b in range(16):
+                par ^= ((lo >> b) & 1).view(-1, 1) * ((z >> b) & 1).view(1, -1)
+            return 1.0 - 2.0 * par.double()
+
+        s_lo, s_hi = signs(0), signs(16)
+
+        def dense_expectation():
+            return ((dense_projection().T @ s_hi) * s_lo).sum(0).cpu().numpy()  # key = row << 16 | column
+
+        res["dense_projected_expectation_8"] = dict(timed(torch, dense_expectation, reps=3, warm=1),
+                                                    max_abs_diff=float(np.abs(dense_expectation() - got_e).max()))
+        print("dense expectation", res["dense_projected_expectation_8"], flush=True)
+        res["dense_projected_sample_20000"] = timed(torch, dense_sample, reps=3, warm=1)
+        print("dense sample", res["dense_projected_sample_20000"], flush=True)
+    print(json.dumps(res, indent=1), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--projection", action="store_true",
                     help="the nearest-probability-distribution leg only (see projection_leg)")
+    ap.add_argument("--projected", action="store_true",
+                    help="the projection-as-a-distribution leg only (see projected_leg)")
     ap.add_argument("--channels", action="store_true", help="the per-clbit channels leg only (see channels_leg)")
     ap.add_argument("--scan", action="store_true", help="the streamed-scan leg only (see scan_leg)")
     ap.add_argument("--moments", action="store_true", help="the second-moments leg only (see moments_leg)")
@@ -704,6 +837,8 @@ def main():
         return scan_leg(args)
     if args.projection:
         return projection_leg(args)
+    if args.projected:
+        return projected_leg(args)
     if args.channels:
         return channels_leg(args)
     import torch
