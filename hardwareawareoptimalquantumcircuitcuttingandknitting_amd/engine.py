@@ -648,6 +648,45 @@ def reduce_labels(ctx: Context, pjob, off_t, n_labels: int, q=None):
 REDUCE_BITS_BATCH = 16  # QK_REDUCE_BITS_BATCH: flip masks per launch (one read of the source each)
 
 
+def _row_operand(name: str, X, m: int | None = None, *, empty_ok: bool = False, on_device: bool = True) -> tuple:
+    """``(rows, m, ld)`` of the operand ``name`` of a row kernel: a float64 ``[rows, >= 2^m]`` with unit column
+    stride whose rows start ``ld >= 2^m`` doubles apart. ``m=None``: from the column count, which must then be a
+    power of two. ``empty_ok``: no row at all is allowed; ``on_device``: the tensor must be on a HIP device.
+    ``ValueError`` before any launch."""
+    if X.dim() != 2 or X.dtype != torch().float64 or X.shape[0] < (0 if empty_ok else 1) or (
+            X.shape[1] > 1 and X.stride(1) != 1) or (on_device and not X.is_cuda):
+        raise ValueError(f"{name} must be a {'device ' if on_device else ''}float64 [rows{'' if empty_ok else ' >= 1'}, "
+                         f">= 2^m] with unit column stride")
+    rows, cols = X.shape
+    if m is None:
+        if cols < 1 or cols & (cols - 1):
+            raise ValueError(f"{name} has {cols} columns, not a power of two, and no m says how many of them count")
+        m = cols.bit_length() - 1
+    m = int(m)
+    if not 0 <= m <= 30:
+        raise ValueError(f"m must be in 0..30, not {m} ({name})")
+    if cols < 1 << m:
+        raise ValueError(f"{name} has {cols} columns for m = {m}")
+    ld = X.stride(0) if rows > 1 else max(X.stride(0), 1 << m)  # the stride of a single row means nothing
+    if ld < 1 << m:
+        raise ValueError(f"row stride of {name} below 2^m = {1 << m}")
+    return rows, m, ld
+
+
+def _rows_overlap(p: int, rows: int, ld: int, cols: int, q: int, rows_q: int, ld_q: int, cols_q: int) -> bool:
+    """Whether two blocks of float64 rows, each ``(address, rows, row stride, columns)``, share a byte."""
+    return p < q + ((rows_q - 1) * ld_q + cols_q) * 8 and q < p + ((rows - 1) * ld + cols) * 8
+
+
+def _workspace(ctx: Context, query: str, *shape, device):
+    """``(work, bytes)``: what the entry ``query`` (a ``qk_*_workspace_bytes``) asks for the launch of ``shape``, as
+    a float64 tensor on ``device`` (``None`` when it asks for nothing) and its size in bytes."""
+    T = torch()
+    need = ctypes.c_int64()
+    ctx.check(getattr(ctx.lib, query)(*shape, ctypes.byref(need)), query)
+    return (T.empty(need.value // 8, dtype=T.float64, device=device) if need.value else None), need.value
+
+
 def reduce_bits(ctx: Context, src, m: int, keep_mask: int, flips, out=None):
     """``qk_reduce_bits``: ``out[r, j * 2^k + y] = sum over x < 2^m with pext(x, keep_mask) == y of
     (-1)^popcount(x & flips[j]) * src[r, x]`` (k = popcount(keep_mask)) -> ``[rows, len(flips) * 2^k]``.
@@ -658,7 +697,7 @@ def reduce_bits(ctx: Context, src, m: int, keep_mask: int, flips, out=None):
     T = torch()
     flips = [int(f) for f in flips]
     m, keep_mask = int(m), int(keep_mask)
-    if not 0 <= m <= 30:
+    if not 0 <= m <= 30:  # here as well: the masks are checked against m before src is looked at
         raise ValueError(f"m must be in 0..30, not {m}")
     if keep_mask < 0 or keep_mask >> m:
         raise ValueError(f"keep_mask {keep_mask:#x} outside the {m} bits")
@@ -669,11 +708,8 @@ def reduce_bits(ctx: Context, src, m: int, keep_mask: int, flips, out=None):
             raise ValueError(f"flip mask {f:#x} outside the {m} bits")
         if f & keep_mask:
             raise ValueError(f"flip mask {f:#x} overlaps keep_mask {keep_mask:#x}")
-    if src.dim() != 2 or src.dtype != T.float64 or src.shape[1] < (1 << m) or (src.shape[1] > 1 and src.stride(1) != 1):
-        raise ValueError("src must be float64 [rows, >= 2^m] with unit column stride")
-    rows = src.shape[0]
-    ld_src = src.stride(0) if rows > 1 else max(src.stride(0), 1 << m)
-    width = len(flips) << bin(keep_mask).count("1")
+    rows, m, ld_src = _row_operand("src", src, m, empty_ok=True, on_device=False)
+    width = len(flips) << keep_mask.bit_count()
     if out is None:
         out = T.empty((rows, width), dtype=T.float64, device=src.device)
     if out.dim() != 2 or out.dtype != T.float64 or out.shape[0] != rows or out.shape[1] < width or (
@@ -682,13 +718,10 @@ def reduce_bits(ctx: Context, src, m: int, keep_mask: int, flips, out=None):
     ld_dst = out.stride(0) if rows > 1 else max(out.stride(0), width)
     if rows == 0:
         return out
-    need = ctypes.c_int64()
-    ctx.check(ctx.lib.qk_reduce_bits_workspace_bytes(rows, m, keep_mask, len(flips), ctypes.byref(need)),
-              "qk_reduce_bits_workspace_bytes")
-    work = T.empty(need.value // 8, dtype=T.float64, device=src.device) if need.value else None
+    work, work_bytes = _workspace(ctx, "qk_reduce_bits_workspace_bytes", rows, m, keep_mask, len(flips), device=src.device)
     masks = (ctypes.c_uint64 * len(flips))(*flips)
     ctx.check(ctx.lib.qk_reduce_bits(ctx.handle, rows, m, src.data_ptr(), ld_src, keep_mask, len(flips), masks,
-                                     out.data_ptr(), ld_dst, _ptr(work), need.value), "qk_reduce_bits")
+                                     out.data_ptr(), ld_dst, _ptr(work), work_bytes), "qk_reduce_bits")
     return out
 
 
@@ -696,34 +729,16 @@ def _row_transform_args(src, m, out):
     """The argument checks :func:`wht_rows` and :func:`kron2_rows` share: ``(rows, m, ld_src, out, ld_dst)``, with
     ``out`` allocated ``[rows, 2^m]`` if it was None. ``ValueError`` before any launch."""
     T = torch()
-    if src.dim() != 2 or src.dtype != T.float64 or (src.shape[1] > 1 and src.stride(1) != 1):
-        raise ValueError("src must be float64 [rows, >= 2^m] with unit column stride")
-    if m is None:
-        cols = src.shape[1]
-        if cols < 1 or cols & (cols - 1):
-            raise ValueError(f"src has {cols} columns, not a power of two: pass m")
-        m = cols.bit_length() - 1
-    m = int(m)
-    if not 0 <= m <= 30:
-        raise ValueError(f"m must be in 0..30, not {m}")
+    rows, m, ld_src = _row_operand("src", src, m, empty_ok=True, on_device=False)
     n = 1 << m
-    if src.shape[1] < n:
-        raise ValueError("src must be float64 [rows, >= 2^m] with unit column stride")
-    rows = src.shape[0]
-    ld_src = src.stride(0) if rows > 1 else max(src.stride(0), n)
-    if out is None:
-        out = T.empty((rows, n), dtype=T.float64, device=src.device)
-    if out.dim() != 2 or out.dtype != T.float64 or out.shape[0] != rows or out.shape[1] < n or (
-            out.shape[1] > 1 and out.stride(1) != 1) or out.device != src.device:
-        raise ValueError("out must be float64 [rows, >= 2^m] with unit column stride, on the device of src")
-    ld_dst = out.stride(0) if rows > 1 else max(out.stride(0), n)
-    if ld_src < n or ld_dst < n:
-        raise ValueError(f"row stride below 2^m = {n}")
-    if rows and not (src.data_ptr() == out.data_ptr() and ld_src == ld_dst):
-        s0, d0 = src.data_ptr(), out.data_ptr()
-        s1, d1 = s0 + ((rows - 1) * ld_src + n) * 8, d0 + ((rows - 1) * ld_dst + n) * 8
-        if s0 < d1 and d0 < s1:
-            raise ValueError("src and out overlap: only out = src (same rows, same stride) transforms in place")
+    if out is None:  # a fresh contiguous tensor: nothing to check
+        return rows, m, ld_src, T.empty((rows, n), dtype=T.float64, device=src.device), n
+    if out.shape[:1] != (rows,) or out.device != src.device:
+        raise ValueError(f"out must have the {rows} rows of src and be on its device")
+    _, _, ld_dst = _row_operand("out", out, m, empty_ok=True, on_device=False)
+    if rows and not (src.data_ptr() == out.data_ptr() and ld_src == ld_dst) and _rows_overlap(
+            src.data_ptr(), rows, ld_src, n, out.data_ptr(), rows, ld_dst, n):
+        raise ValueError("src and out overlap: only out = src (same rows, same stride) transforms in place")
     return rows, m, ld_src, out, ld_dst
 
 
@@ -769,30 +784,13 @@ def transpose_rows(ctx: Context, X, m: int | None = None, out=None):
     read; ``m`` defaults to its column count, which must then be a power of two. ``out`` (optional): a
     contiguous float64 ``[2^m, ldt]`` on the device of ``X`` that does not overlap it."""
     T = torch()
-    if X.dim() != 2 or X.dtype != T.float64 or X.shape[0] < 1 or (X.shape[1] > 1 and X.stride(1) != 1) or not X.is_cuda:
-        raise ValueError("X must be a device float64 [K >= 1, >= 2^m] with unit column stride")
-    K = X.shape[0]
-    if m is None:
-        cols = X.shape[1]
-        if cols < 1 or cols & (cols - 1):
-            raise ValueError(f"X has {cols} columns, not a power of two: pass m")
-        m = cols.bit_length() - 1
-    m = int(m)
-    if not 0 <= m <= 30:
-        raise ValueError(f"m must be in 0..30, not {m}")
-    n = 1 << m
-    if X.shape[1] < n:
-        raise ValueError(f"X has {X.shape[1]} columns for m = {m}")
-    ldx = X.stride(0) if K > 1 else max(X.stride(0), n)
-    if ldx < n:
-        raise ValueError(f"row stride below 2^m = {n}")
-    ldt = -(-K // 16) * 16
+    K, m, ldx = _row_operand("X", X, m)
+    n, ldt = 1 << m, -(-K // 16) * 16
     if out is None:
         out = T.empty((n, ldt), dtype=T.float64, device=X.device)
     if out.dtype != T.float64 or tuple(out.shape) != (n, ldt) or not out.is_contiguous() or out.device != X.device:
         raise ValueError(f"out must be a contiguous float64 [{n}, {ldt}] on the device of X")
-    s0, d0 = X.data_ptr(), out.data_ptr()
-    if s0 < d0 + n * ldt * 8 and d0 < s0 + ((K - 1) * ldx + n) * 8:
+    if _rows_overlap(X.data_ptr(), K, ldx, n, out.data_ptr(), n, ldt, ldt):
         raise ValueError("X and out overlap")
     ctx.check(ctx.lib.qk_transpose_rows(ctx.handle, K, m, X.data_ptr(), ldx, out.data_ptr(), ldt), "qk_transpose_rows")
     return out
@@ -855,27 +853,11 @@ def gram_rows(ctx: Context, A, B=None, m: int | None = None, out=None):
     T = torch()
     if B is None:
         B = A
-    for name, X in (("A", A), ("B", B)):
-        if X.dim() != 2 or X.dtype != T.float64 or X.shape[0] < 1 or (X.shape[1] > 1 and X.stride(1) != 1) or not X.is_cuda:
-            raise ValueError(f"{name} must be a device float64 [rows >= 1, >= 2^m] with unit column stride")
+    RA, m, lda = _row_operand("A", A, m)
+    RB, _, ldb = _row_operand("B", B, m)
     if B.device != A.device:
         raise ValueError("A and B must be on one device")
-    if m is None:
-        cols = A.shape[1]
-        if cols < 1 or cols & (cols - 1):
-            raise ValueError(f"A has {cols} columns, not a power of two: pass m")
-        m = cols.bit_length() - 1
-    m = int(m)
-    if not 0 <= m <= 30:
-        raise ValueError(f"m must be in 0..30, not {m}")
     n = 1 << m
-    if A.shape[1] < n or B.shape[1] < n:
-        raise ValueError(f"A has {A.shape[1]} and B {B.shape[1]} columns for m = {m}")
-    RA, RB = A.shape[0], B.shape[0]
-    lda = A.stride(0) if RA > 1 else max(A.stride(0), n)
-    ldb = B.stride(0) if RB > 1 else max(B.stride(0), n)
-    if lda < n or ldb < n:
-        raise ValueError(f"row stride below 2^m = {n}")
     if out is None:
         out = T.empty((RA, RB), dtype=T.float64, device=A.device)
     if out.dim() != 2 or out.dtype != T.float64 or tuple(out.shape) != (RA, RB) or (RB > 1 and out.stride(1) != 1) or (
@@ -884,16 +866,12 @@ def gram_rows(ctx: Context, A, B=None, m: int | None = None, out=None):
     ldg = out.stride(0) if RA > 1 else max(out.stride(0), RB)
     if ldg < RB:
         raise ValueError(f"row stride of out below {RB}")
-    g0 = out.data_ptr()
-    g1 = g0 + ((RA - 1) * ldg + RB) * 8
     for X, rows, ld in ((A, RA, lda), (B, RB, ldb)):
-        if X.data_ptr() < g1 and g0 < X.data_ptr() + ((rows - 1) * ld + n) * 8:
+        if _rows_overlap(X.data_ptr(), rows, ld, n, out.data_ptr(), RA, ldg, RB):
             raise ValueError("out overlaps A or B")
-    need = ctypes.c_int64()
-    ctx.check(ctx.lib.qk_gram_rows_workspace_bytes(RA, RB, m, ctypes.byref(need)), "qk_gram_rows_workspace_bytes")
-    work = T.empty(need.value // 8, dtype=T.float64, device=A.device) if need.value else None
+    work, work_bytes = _workspace(ctx, "qk_gram_rows_workspace_bytes", RA, RB, m, device=A.device)
     ctx.check(ctx.lib.qk_gram_rows(ctx.handle, RA, RB, m, A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldg,
-                                   _ptr(work), need.value), "qk_gram_rows")
+                                   _ptr(work), work_bytes), "qk_gram_rows")
     return out
 
 
@@ -905,26 +883,59 @@ _SCAN_NSTATS, _SCAN_NCOUNTS, _SCAN_ENTROPY = 16, 4, 1
 
 
 def _scan_side(name: str, X, K: int | None = None):
-    """``(K, m, ld)`` of a scan operand: a device float64 ``[K, 2^m]`` with unit column stride."""
-    T = torch()
-    if X.dim() != 2 or X.dtype != T.float64 or not X.is_cuda or X.shape[0] < 1 or X.shape[1] < 1 or (
-            X.shape[1] > 1 and X.stride(1) != 1):
-        raise ValueError(f"{name} must be a device float64 [K >= 1, 2^m] with unit column stride")
-    cols = X.shape[1]
-    if cols & (cols - 1) or cols > 1 << 30:
-        raise ValueError(f"{name} has {cols} columns, not a power of two up to 2^30")
-    if K is not None and X.shape[0] != K:
-        raise ValueError(f"{name} has {X.shape[0]} rows for {K} terms")
-    ld = X.stride(0) if X.shape[0] > 1 else max(X.stride(0), cols)
-    if ld < cols:
-        raise ValueError(f"row stride of {name} below its {cols} columns")
-    return X.shape[0], cols.bit_length() - 1, ld
+    """``(K, m, ld)`` of a scan operand: a device float64 ``[K, 2^m]`` with unit column stride (every column counts:
+    ``m`` is that of the column count), of ``K`` terms if ``K`` is given."""
+    rows, m, ld = _row_operand(name, X)
+    if K is not None and rows != K:
+        raise ValueError(f"{name} has {rows} rows for {K} terms")
+    return rows, m, ld
+
+
+def _scan_sides(A, B, names: tuple = ("A", "B")) -> tuple:
+    """``(K, ma, lda, mb, ldb)`` of the two sides of a knit (:func:`_scan_side`), which share the terms and the device."""
+    K, ma, lda = _scan_side(names[0], A)
+    _, mb, ldb = _scan_side(names[1], B, K)
+    if B.device != A.device:
+        raise ValueError(f"{names[0]} and {names[1]} must be on one device")
+    return K, ma, lda, mb, ldb
+
+
+def _second_knit(A, ma: int, mb: int, A2, B2) -> tuple:
+    """``(K2, lda2, ldb2)`` of the optional second knit of a pair scan, on the outputs and the device of the first
+    (whose side A is ``A [K, 2^ma]``); zeros without one."""
+    if A2 is None and B2 is None:
+        return 0, 0, 0
+    if A2 is None or B2 is None:
+        raise ValueError("a second knit needs both A2 and B2")
+    K2, ma2, lda2, mb2, ldb2 = _scan_sides(A2, B2, ("A2", "B2"))
+    if (ma2, mb2) != (ma, mb) or A2.device != A.device:
+        raise ValueError(f"the second knit is 2^{ma2} x 2^{mb2}, the first 2^{ma} x 2^{mb} (or another device)")
+    return K2, lda2, ldb2
 
 
 def scan_slabs(ma: int, mb: int) -> list:
     """The ``[i_begin, i_end)`` ranges of side A that the scan walks: at most ``SCAN_SLAB_OUTPUTS`` outputs each."""
     rows = max(1, SCAN_SLAB_OUTPUTS >> mb)
     return [(i, min(i + rows, 1 << ma)) for i in range(0, 1 << ma, rows)]
+
+
+def sum_slabs(stats: np.ndarray) -> np.ndarray:
+    """float64 ``[n]``: the columns of per-slab values ``stats [slabs, n]`` summed in ascending slab order, every
+    column the chain ``acc = acc + v`` from 0.0."""
+    acc = np.zeros(stats.shape[1])
+    for row in stats:  # ascending slabs
+        acc = acc + row
+    return acc
+
+
+def combine_slabs(names: tuple, stats: np.ndarray, maxima: tuple = (), minima: tuple = ()) -> dict:
+    """``{name: float}`` from per-slab statistics ``stats [slabs, >= len(names)]``, column ``i`` holding ``names[i]``:
+    the maximum or the minimum over the slabs for the names listed as such, else the sum (:func:`sum_slabs`)."""
+    stats = stats[:, :len(names)]
+    out = dict(zip(names, sum_slabs(stats).tolist()))
+    out.update({name: float(stats[:, names.index(name)].max()) for name in maxima})
+    out.update({name: float(stats[:, names.index(name)].min()) for name in minima})
+    return out
 
 
 def knit_scan(ctx: Context, A, B, A2=None, B2=None, *, tau: float = 0.0, entropy: bool = False, hist: bool = False) -> dict:
@@ -937,19 +948,8 @@ def knit_scan(ctx: Context, A, B, A2=None, B2=None, *, tau: float = 0.0, entropy
     every ``p > 0``; ``None`` without ``hist=True``). Side A is walked in slabs of at most ``SCAN_SLAB_OUTPUTS``
     outputs; the slabs' statistics are combined in ascending order in float64 on the host."""
     T = torch()
-    K, ma, lda = _scan_side("A", A)
-    _, mb, ldb = _scan_side("B", B, K)
-    pair = A2 is not None or B2 is not None
-    K2 = lda2 = ldb2 = 0
-    if pair:
-        if A2 is None or B2 is None:
-            raise ValueError("a second knit needs both A2 and B2")
-        K2, ma2, lda2 = _scan_side("A2", A2)
-        _, mb2, ldb2 = _scan_side("B2", B2, K2)
-        if (ma2, mb2) != (ma, mb) or A2.device != A.device or B2.device != A.device:
-            raise ValueError(f"the second knit is 2^{ma2} x 2^{mb2}, the first 2^{ma} x 2^{mb} (or another device)")
-    if B.device != A.device:
-        raise ValueError("A and B must be on one device")
+    K, ma, lda, mb, ldb = _scan_sides(A, B)
+    K2, lda2, ldb2 = _second_knit(A, ma, mb, A2, B2)
     tau = float(tau)
     if tau != tau:
         raise ValueError("tau is not a number")
@@ -958,27 +958,15 @@ def knit_scan(ctx: Context, A, B, A2=None, B2=None, *, tau: float = 0.0, entropy
     stats = T.empty((len(slabs), _SCAN_NSTATS), dtype=T.float64, device=dev)
     counts = T.empty((len(slabs), _SCAN_NCOUNTS), dtype=T.int64, device=dev)
     hists = T.empty((len(slabs), SCAN_BINS), dtype=T.int64, device=dev) if hist else None
-    need = ctypes.c_int64()
-    ctx.check(ctx.lib.qk_knit_scan_workspace_bytes(ma, mb, *slabs[0], ctypes.byref(need)), "qk_knit_scan_workspace_bytes")
-    work = T.empty(need.value // 8, dtype=T.float64, device=dev)  # the first slab is the largest
+    # the first slab is the largest
+    work, work_bytes = _workspace(ctx, "qk_knit_scan_workspace_bytes", ma, mb, *slabs[0], device=dev)
     for s, (i0, i1) in enumerate(slabs):
         ctx.check(ctx.lib.qk_knit_scan(ctx.handle, K, ma, mb, A.data_ptr(), lda, B.data_ptr(), ldb, K2, _ptr(A2), lda2,
                                        _ptr(B2), ldb2, i0, i1, _SCAN_ENTROPY if entropy else 0, tau,
                                        stats[s].data_ptr(), counts[s].data_ptr(), _ptr(hists[s]) if hist else None,
-                                       work.data_ptr(), need.value), "qk_knit_scan")
+                                       _ptr(work), work_bytes), "qk_knit_scan")
     st, ct = stats.cpu().numpy(), counts.cpu().numpy()
-    out = {}
-    for slot, name in enumerate(SCAN_STATS):
-        col = st[:, slot]
-        if name in ("max", "maxd"):
-            out[name] = float(col.max())
-        elif name == "min":
-            out[name] = float(col.min())
-        else:
-            acc = np.float64(0.0)
-            for v in col:  # ascending slabs
-                acc = acc + v
-            out[name] = float(acc)
+    out = combine_slabs(SCAN_STATS, st, maxima=("max", "maxd"), minima=("min",))
     out["count_tau"], out["count_pos"] = int(ct[:, 0].sum()), int(ct[:, 1].sum())
     # the slabs ascend in flat index: the first slab that holds the extreme value holds its lowest index
     out["argmax"] = int(ct[int(np.argmax(st[:, 5])), 2])
@@ -993,10 +981,7 @@ def knit_collect(ctx: Context, A, B, tau: float, capacity: int):
     and the Python int ``count`` of such outputs. ``count`` may exceed ``capacity``; the tensors then hold
     ``capacity`` of the outputs. The values are bit-identical to those the scan sees."""
     T = torch()
-    K, ma, lda = _scan_side("A", A)
-    _, mb, ldb = _scan_side("B", B, K)
-    if B.device != A.device:
-        raise ValueError("A and B must be on one device")
+    K, ma, lda, mb, ldb = _scan_sides(A, B)
     capacity, tau = int(capacity), float(tau)
     if capacity < 0 or tau != tau:
         raise ValueError(f"capacity {capacity} must not be negative and tau {tau} must be a number")
@@ -1043,44 +1028,22 @@ def knit_project_scan(ctx: Context, A, B, A2=None, B2=None, *, theta: float = 0.
     walked in slabs of at most ``SCAN_SLAB_OUTPUTS`` outputs; the slabs are combined in ascending order in float64
     on the host."""
     T = torch()
-    K, ma, lda = _scan_side("A", A)
-    _, mb, ldb = _scan_side("B", B, K)
-    pair = A2 is not None or B2 is not None
-    K2 = lda2 = ldb2 = 0
-    if pair:
-        if A2 is None or B2 is None:
-            raise ValueError("a second knit needs both A2 and B2")
-        K2, ma2, lda2 = _scan_side("A2", A2)
-        _, mb2, ldb2 = _scan_side("B2", B2, K2)
-        if (ma2, mb2) != (ma, mb) or A2.device != A.device or B2.device != A.device:
-            raise ValueError(f"the second knit is 2^{ma2} x 2^{mb2}, the first 2^{ma} x 2^{mb} (or another device)")
-    if B.device != A.device:
-        raise ValueError("A and B must be on one device")
+    K, ma, lda, mb, ldb = _scan_sides(A, B)
+    K2, lda2, ldb2 = _second_knit(A, ma, mb, A2, B2)
     theta, theta2, accuracy = check_projection_args(theta, theta2, accuracy)
     slabs = scan_slabs(ma, mb)
     dev = A.device
     stats = T.empty((len(slabs), _PROJ_NSTATS), dtype=T.float64, device=dev)
     counts = T.empty((len(slabs), _PROJ_NCOUNTS), dtype=T.int64, device=dev)
-    need = ctypes.c_int64()
-    ctx.check(ctx.lib.qk_knit_project_scan_workspace_bytes(ma, mb, *slabs[0], ctypes.byref(need)),
-              "qk_knit_project_scan_workspace_bytes")
-    work = T.empty(need.value // 8, dtype=T.float64, device=dev)  # the first slab is the largest
+    # the first slab is the largest
+    work, work_bytes = _workspace(ctx, "qk_knit_project_scan_workspace_bytes", ma, mb, *slabs[0], device=dev)
     for s, (i0, i1) in enumerate(slabs):
         ctx.check(ctx.lib.qk_knit_project_scan(ctx.handle, K, ma, mb, A.data_ptr(), lda, B.data_ptr(), ldb, K2, _ptr(A2),
                                                lda2, _ptr(B2), ldb2, i0, i1, _PROJ_ENTROPY if entropy else 0, theta,
                                                theta2, accuracy, stats[s].data_ptr(), counts[s].data_ptr(),
-                                               work.data_ptr(), need.value), "qk_knit_project_scan")
+                                               _ptr(work), work_bytes), "qk_knit_project_scan")
     st, ct = stats.cpu().numpy(), counts.cpu().numpy()
-    out = {}
-    for slot, name in enumerate(PROJ_STATS):
-        col = st[:, slot]
-        if name in ("pmax", "pmax2", "maxd"):
-            out[name] = float(col.max())
-        else:
-            acc = np.float64(0.0)
-            for v in col:  # ascending slabs
-                acc = acc + v
-            out[name] = float(acc)
+    out = combine_slabs(PROJ_STATS, st, maxima=("pmax", "pmax2", "maxd"))
     for slot, name in enumerate(PROJ_COUNTS):
         out[name] = int(ct[:, slot].sum())
     # the slabs ascend in flat index: the first slab that holds the maximum holds its lowest index
@@ -1093,10 +1056,7 @@ PROJ_TILE_MASKS = 8  # QK_PROJ_TILE_MASKS
 
 def _project_range(A, B, i_begin, i_end) -> tuple:
     """``(K, ma, lda, mb, ldb, i_begin, i_end, tiles)`` of a tiles / draw call on ``[i_begin, i_end)``."""
-    K, ma, lda = _scan_side("A", A)
-    _, mb, ldb = _scan_side("B", B, K)
-    if B.device != A.device:
-        raise ValueError("A and B must be on one device")
+    K, ma, lda, mb, ldb = _scan_sides(A, B)
     i_begin, i_end = int(i_begin), (1 << ma if i_end is None else int(i_end))
     if not 0 <= i_begin < i_end <= 1 << ma:
         raise ValueError(f"need 0 <= i_begin < i_end <= 2^{ma}, not [{i_begin}, {i_end})")
@@ -1148,14 +1108,11 @@ def knit_project_draw(ctx: Context, A, B, theta: float, accuracy: float, W, u, i
     flat = T.empty(n, dtype=T.int64, device=A.device)
     pval = T.empty(n, dtype=T.float64, device=A.device)
     total = T.empty(1, dtype=T.float64, device=A.device)
-    need = ctypes.c_int64()
-    ctx.check(ctx.lib.qk_knit_project_draw_workspace_bytes(ma, mb, i_begin, i_end, ctypes.byref(need)),
-              "qk_knit_project_draw_workspace_bytes")
-    work = T.empty(need.value // 8, dtype=T.float64, device=A.device)
+    work, work_bytes = _workspace(ctx, "qk_knit_project_draw_workspace_bytes", ma, mb, i_begin, i_end, device=A.device)
     ctx.check(ctx.lib.qk_knit_project_draw(ctx.handle, K, ma, mb, A.data_ptr(), lda, B.data_ptr(), ldb, i_begin, i_end,
                                            theta, accuracy, W.data_ptr(), n, _ptr(u) if n else None,
                                            _ptr(flat) if n else None, _ptr(pval) if n else None, total.data_ptr(),
-                                           work.data_ptr(), need.value), "qk_knit_project_draw")
+                                           _ptr(work), work_bytes), "qk_knit_project_draw")
     return flat, pval, float(total[0])
 
 

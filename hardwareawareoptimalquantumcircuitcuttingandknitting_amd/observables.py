@@ -43,6 +43,7 @@ up to ``2^(N-k)`` entries, so that bound does not carry over.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -79,8 +80,14 @@ def pdep(v: int, mask: int) -> int:
     return out
 
 
-def _parity(x) -> int:
-    return bin(int(x)).count("1") & 1
+def popcount(x) -> np.ndarray:
+    """The number of set bits of every entry of a non-negative integer array (a Python int has ``bit_count``)."""
+    x = np.asarray(x, dtype=np.int64)
+    n = np.zeros_like(x)
+    while np.any(x):
+        n += x & 1
+        x = x >> 1
+    return n
 
 
 def reduce_bits_shape(rows: int, m: int, keep_mask: int, tile_bits: int = 10, min_groups: int = 256) -> dict:
@@ -89,7 +96,7 @@ def reduce_bits_shape(rows: int, m: int, keep_mask: int, tile_bits: int = 10, mi
     lo, hi = (1 << t) - 1, (1 << (m - t)) - 1
     keep_lo, drop_lo = keep_mask & lo, ~keep_mask & lo
     keep_hi, drop_hi = (keep_mask >> t) & hi, ~(keep_mask >> t) & hi
-    klo, khi, dhi = bin(keep_lo).count("1"), bin(keep_hi).count("1"), bin(drop_hi).count("1")
+    klo, khi, dhi = keep_lo.bit_count(), keep_hi.bit_count(), drop_hi.bit_count()
     groups, split = rows << khi, 1
     while groups * split < min_groups and split < (1 << dhi):
         split *= 2
@@ -119,14 +126,14 @@ def reduce_bits_host(src: np.ndarray, m: int, keep_mask: int, flips, tile_bits: 
         for yhi in range(1 << khi):
             base_hi = pdep(yhi, sh["keep_hi"])
             for j, f in enumerate(flips):
-                lane = np.array([_parity(int(x) & f) for x in xl])
+                lane = popcount(xl & f) & 1
                 total = None
                 for s in range(sh["split"]):
                     sub = pdep(s * chunk, sh["drop_hi"])
                     part = np.zeros(1 << klo)
                     for _ in range(chunk):
                         tile = base_hi | sub
-                        neg = lane ^ _parity((tile << t) & f)
+                        neg = lane ^ (((tile << t) & f).bit_count() & 1)
                         v = src[r, tile * T:(tile + 1) * T]
                         np.add.at(part, yl, np.where(neg == 1, -v, v))
                         sub = ((sub | ~sh["drop_hi"]) + 1) & sh["drop_hi"]
@@ -146,6 +153,15 @@ def check_clbits(clbits, n_clbits: int) -> list:
         if not 0 <= c < n_clbits:
             raise ValueError(f"clbit {c} outside 0..{n_clbits - 1}")
     return out
+
+
+def check_not_negative(name: str, value, kind=int):
+    """``kind(value)`` (``int`` for a count, ``float`` for a bound), else ``ValueError`` when it is negative or no
+    number."""
+    v = kind(value)
+    if not v >= 0:
+        raise ValueError(f"{name} must not be negative, not {v}")
+    return v
 
 
 def parse_masks(masks, n_clbits: int) -> list:
@@ -190,22 +206,36 @@ def split_mask(mask: int, fragment_clbits: list) -> list:
     return [sum(1 << i for i, c in enumerate(fcl) if mask >> c & 1) for fcl in fragment_clbits]
 
 
+def _is_tensor(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _check_range(what: str, lo: int, hi: int, n_bits: int) -> None:
+    """``ValueError`` unless ``lo`` and ``hi``, the least and the greatest of a batch, lie in ``0 .. 2^n_bits - 1``."""
+    if lo < 0 or hi >> n_bits:
+        raise ValueError(f"{what} {hi if lo >= 0 else lo:#x} outside 0..2^{n_bits} - 1")
+
+
+def _int64_vector(what: str, values: np.ndarray, n_bits: int) -> np.ndarray:
+    """An integer numpy array of at most one dimension as a contiguous ``int64`` ``[M]``, every entry in
+    ``0 .. 2^n_bits - 1`` (checked before the conversion: a uint64 at or above 2^63 is out of range)."""
+    if values.dtype.kind not in "iu":
+        raise ValueError(f"a {what} array must hold integers, not {values.dtype}")
+    if values.ndim > 1:
+        raise ValueError(f"a {what} array must be one-dimensional, not {values.shape}")
+    if values.size:
+        _check_range(what, int(values.min()), int(values.max()), n_bits)
+    return np.ascontiguousarray(values.reshape(-1), dtype=np.int64)
+
+
 def masks_array(masks, n_clbits: int) -> np.ndarray:
     """Z-string observables as an ``int64`` array ``[M]`` of masks over clbits ``0..n_clbits-1``. An
     integer numpy array or a torch int64 tensor (of any number of masks) is checked vectorised;
     anything else (ints, ``'IZ'`` strings, lists of them) goes through :func:`parse_masks`."""
-    if type(masks).__module__.split(".")[0] == "torch":
+    if _is_tensor(masks):
         masks = masks.detach().cpu().numpy()
     if isinstance(masks, np.ndarray):
-        if masks.dtype.kind not in "iu":
-            raise ValueError(f"a mask array must hold integers, not {masks.dtype}")
-        if masks.ndim > 1:
-            raise ValueError(f"a mask array must be one-dimensional, not {masks.shape}")
-        zs = np.ascontiguousarray(masks.reshape(-1), dtype=np.int64)  # a uint64 at or above 2^63 turns negative
-        if zs.size and (int(zs.min()) < 0 or int(zs.max()) >> n_clbits):
-            bad = zs[(zs < 0) | ((zs >> min(n_clbits, 63)) != 0)][0]
-            raise ValueError(f"mask {int(bad):#x} outside the {n_clbits} clbits")
-        return zs
+        return _int64_vector("mask", masks, n_clbits)
     return np.array(parse_masks(masks, n_clbits), dtype=np.int64).reshape(-1)
 
 
@@ -366,11 +396,7 @@ def keys_array(keys, n_bits: int):
     lists of ints and integer numpy arrays give a numpy array; a torch int64 tensor stays a tensor on its
     device and is range-checked there (one min / max sync). ``ValueError`` for a key outside the range, a
     non-integer dtype or more than one dimension."""
-    def outside(lo, hi):
-        if lo < 0 or hi >> n_bits:
-            raise ValueError(f"key {hi if lo >= 0 else lo:#x} outside 0..2^{n_bits} - 1")
-
-    if type(keys).__module__.split(".")[0] == "torch":
+    if _is_tensor(keys):
         import torch as T
 
         if keys.dtype != T.int64:
@@ -380,24 +406,16 @@ def keys_array(keys, n_bits: int):
         ks = keys.detach().reshape(-1).contiguous()
         if ks.numel():
             lo, hi = T.aminmax(ks)
-            outside(int(lo), int(hi))
+            _check_range("key", int(lo), int(hi), n_bits)
         return ks
-    if isinstance(keys, (int, np.integer)):
-        keys = [keys]
-    if not isinstance(keys, np.ndarray):
-        keys = list(keys)
-        if not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in keys):
-            raise ValueError("keys must be integers")
-        if keys:
-            outside(min(int(k) for k in keys), max(int(k) for k in keys))
-        return np.array([int(k) for k in keys], dtype=np.int64).reshape(-1)
-    if keys.dtype.kind not in "iu":
-        raise ValueError(f"a key array must hold integers, not {keys.dtype}")
-    if keys.ndim > 1:
-        raise ValueError(f"a key array must be one-dimensional, not {keys.shape}")
-    if keys.size:
-        outside(int(keys.min()), int(keys.max()))
-    return np.ascontiguousarray(keys.reshape(-1), dtype=np.int64)
+    if isinstance(keys, np.ndarray):
+        return _int64_vector("key", keys, n_bits)
+    keys = [keys] if isinstance(keys, (int, np.integer)) else list(keys)
+    if not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in keys):
+        raise ValueError("keys must be integers")
+    if keys:
+        _check_range("key", min(int(k) for k in keys), max(int(k) for k in keys), n_bits)
+    return np.array([int(k) for k in keys], dtype=np.int64).reshape(-1)
 
 
 def knit_at_host(Xs: list, positions: list, keys, dead: int = 0) -> np.ndarray:
@@ -678,19 +696,10 @@ def project_tiles_host(Xs: list, theta: float, accuracy: float, masks=((0, 0),),
     for m, (za, zb) in enumerate(masks):
         if za < 0 or zb < 0 or za >> ma or zb >> mb:
             raise ValueError(f"mask ({za:#x}, {zb:#x}) has a bit outside the sides' {ma} and {mb} bits")
-        sa = 1 - 2 * (_popcount(rows & za) & 1)
-        sb = 1 - 2 * (_popcount(cols & zb) & 1)
+        sa = 1 - 2 * (popcount(rows & za) & 1)
+        sb = 1 - 2 * (popcount(cols & zb) & 1)
         out[m] = (P * sa[:, :, None] * sb[:, None, :]).sum(axis=(1, 2))
     return out
-
-
-def _popcount(x) -> np.ndarray:
-    x = np.asarray(x, dtype=np.int64)
-    n = np.zeros_like(x)
-    while np.any(x):
-        n += x & 1
-        x = x >> 1
-    return n
 
 
 def project_draw_host(Xs: list, theta: float, accuracy: float, u, i_begin: int = 0, i_end: int | None = None) -> tuple:
@@ -737,7 +746,7 @@ def inverse_wht_marginal(values) -> np.ndarray:
     if v.size != 1 << k:
         raise ValueError(f"{v.size} values: not a power of two")
     s = np.arange(v.size)
-    H = 1 - 2 * (_popcount(s[:, None] & s[None, :]) & 1)
+    H = 1 - 2 * (popcount(s[:, None] & s[None, :]) & 1)
     return (H @ v) / v.size
 
 
@@ -814,6 +823,22 @@ def _side_operand(ctx, parts: list, K: int, dev):
     if X is None:
         X = T.ones((K, 1), dtype=T.float64, device=dev)
     return X if scale is None else X * scale
+
+
+class ScanSides(NamedTuple):
+    """What :meth:`KnitReducer._scan_operands` returns: the two sides of the scan of a marginal, each the Khatri-Rao
+    product of its fragments' reduced operands (:func:`scan_sides`, :func:`_side_operand`)."""
+    A: object          # device float64 [K, 2^len(where_a)]
+    B: object          # device float64 [K, 2^len(where_b)]
+    where_a: list      # the key bit of every bit of side A's index
+    where_b: list
+    A2: object = None  # the same sides of another reducer's knit, in this one's bit order
+    B2: object = None
+
+    def key(self, flat):
+        """Flat scan indices ``i << mb | j`` (an int or an int64 tensor) as keys."""
+        mb = len(self.where_b)
+        return deposit_bits(deposit_bits(flat & 0, flat >> mb, self.where_a), flat & ((1 << mb) - 1), self.where_b)
 
 
 @dataclass
@@ -939,16 +964,44 @@ class KnitReducer:
                                             [g.knit_coefficients() for g in vg]).coefficients().sum())
 
     # -- pieces ---------------------------------------------------------------------------------
-    def _operands(self, keep: list, flips: list) -> list:
-        """Per fragment ``[terms, len(flips[f]) * 2^k_f]``: its swept rows reduced, then transformed."""
+    def _clbits(self, clbits) -> list:
+        return list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+
+    def _check_other(self, other) -> None:
+        """``ValueError`` unless ``other`` is a reducer this one's knit can be compared with."""
+        if not isinstance(other, KnitReducer):
+            raise ValueError("other must be a KnitReducer")
+        if other.N != self.N:
+            raise ValueError(f"{self.N} clbits against {other.N}")
+        if other.device != self.device:
+            raise ValueError(f"reducers on devices {self.device} and {other.device}")
+
+    def _reduced(self, keep: list, flips: list | None = None) -> list:
+        """Per fragment ``[R_f, len(flips[f]) * 2^k_f]``: its swept rows reduced onto ``keep[f]``, once per flip mask
+        (``None``: the plain marginal, ``[0]`` for every fragment)."""
         reds = []
-        for q, fcl, kp, fl in zip(self.qs, self.clbits, keep, flips):
+        for q, fcl, kp, fl in zip(self.qs, self.clbits, keep, flips or [[0]] * len(keep)):
             m = len(fcl)
             if kp == (1 << m) - 1 and fl == [0]:  # nothing to sum out
                 reds.append(q)
             else:
                 reds.append(engine.reduce_bits(self.ctx, q, m, kp, fl))
-        return engine.fragment_operands(self.ctx, self.ops, reds)
+        return reds
+
+    def _operands(self, keep: list, flips: list | None = None) -> list:
+        """Per fragment ``[terms, len(flips[f]) * 2^k_f]``: its swept rows reduced (:meth:`_reduced`), then
+        transformed."""
+        return engine.fragment_operands(self.ctx, self.ops, self._reduced(keep, flips))
+
+    def _keyed_operands(self, cl: list) -> tuple:
+        """``(mats, where, K)`` for keys whose bit ``i`` is ``cl[i]``: per fragment its operand reduced onto its
+        clbits in ``cl`` and the key bit of every bit of that operand's column index (:func:`key_positions`), and
+        the number of terms. No fragment at all is one fragment of no bit whose single entry holds ``_scalar``."""
+        if not self.frags:
+            T = engine.torch()
+            return [T.full((1, 1), self._scalar, dtype=T.float64, device=T.device("cuda", self.device))], [[]], 1
+        keep, where = key_positions(cl, self.clbits)
+        return self._operands(keep), where, self.ops.num_terms
 
     def _contract(self, mats: list, positions: list, k: int):
         T = engine.torch()
@@ -961,6 +1014,10 @@ class KnitReducer:
     # -- per-clbit channels ---------------------------------------------------------------------
     def _measured(self) -> set:
         return {c for fcl in self.clbits for c in fcl}
+
+    def _measured_among(self, clbits) -> int:
+        """How many of the chosen clbits (``None``: all) some fragment measures."""
+        return len(self._measured() & set(self._clbits(clbits)))
 
     def with_channels(self, spec) -> "KnitReducer":
         """A reducer of ``R'[y] = sum_x prod_c A_c[y_c][x_c] R[x]``, ``A_c`` the real 2x2 matrix of clbit ``c``
@@ -1003,8 +1060,7 @@ class KnitReducer:
         self.ctx.bind_stream()
         cl = check_clbits(clbits, self.N)
         keep, positions = split_clbits(cl, self.clbits)
-        mats = self._operands(keep, [[0]] * len(keep))
-        return _user_order(engine.torch(), self._contract(mats, positions, len(cl)), cl)
+        return _user_order(engine.torch(), self._contract(self._operands(keep), positions, len(cl)), cl)
 
     def expectation(self, masks, *, method: str = "reduce") -> np.ndarray:
         """float64 ``[M]``: ``sum_key (-1)^popcount(key & mask) R[key]`` of the exact quasi-distribution
@@ -1100,7 +1156,7 @@ class KnitReducer:
     def correlations(self, clbits=None) -> np.ndarray:
         """numpy ``[k, k]``: entry ``(i, j)`` is ``<Z_clbits[i] Z_clbits[j]>``, the diagonal ``<Z_clbits[i]>``;
         symmetric. ``None``: all clbits. The ``k (k + 1) / 2`` strings go through the spectrum route."""
-        cl = list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+        cl = self._clbits(clbits)
         k = len(cl)
         iu, ju = np.triu_indices(k)
         bit = np.left_shift(np.int64(1), np.asarray(cl, dtype=np.int64))
@@ -1121,15 +1177,12 @@ class KnitReducer:
         self.ctx.bind_stream()
         T = engine.torch()
         dev = T.device("cuda", self.device)
-        shots = int(shots)
-        if shots < 0:
-            raise ValueError(f"shots must not be negative, not {shots}")
-        cl = list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+        shots = check_not_negative("shots", shots)
+        cl = self._clbits(clbits)
         keys = T.zeros(shots, dtype=T.int64, device=dev)
         if shots == 0 or not self.frags:
             return keys
-        keep, where = key_positions(cl, self.clbits)
-        mats = self._operands(keep, [[0]] * len(keep))  # X_f [K, 2^k_f]
+        mats, where, _ = self._keyed_operands(cl)  # X_f [K, 2^k_f]
         sums = [engine.reduce_bits(self.ctx, X, len(pos), 0, [0])[:, 0] for X, pos in zip(mats, where)]
         tails = [None] * len(mats)  # t_f[k] = prod_{g > f} s_g[k]
         tail = T.ones(mats[0].shape[0], dtype=T.float64, device=dev)
@@ -1186,7 +1239,7 @@ class KnitReducer:
         as in :meth:`sample`. A key with a bit set on a clbit that no fragment measures has probability 0."""
         self.ctx.bind_stream()
         T = engine.torch()
-        cl = list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+        cl = self._clbits(clbits)
         ks = self._device_keys(keys_array(keys, len(cl)))
         if not self.frags:
             return (ks == 0).to(T.float64) * self._scalar
@@ -1194,8 +1247,7 @@ class KnitReducer:
         if cl == list(range(self.N)):
             Xts, where = self.transposed_operands(), self.clbits
         else:
-            keep, where = key_positions(cl, self.clbits)
-            mats = self._operands(keep, [[0]] * len(keep))
+            mats, where, _ = self._keyed_operands(cl)
             Xts = [engine.transpose_rows(self.ctx, X, len(pos)) for X, pos in zip(mats, where)]
         dead = ((1 << len(cl)) - 1) & ~sum(1 << b for pos in where for b in pos)
         return engine.knit_at(self.ctx, Xts, where, ks, dead)
@@ -1207,9 +1259,7 @@ class KnitReducer:
         p = self.probabilities(keys, clbits)
         if not p.numel():
             raise ValueError("linear_xeb needs at least one key")
-        cl = range(self.N) if clbits is None else clbits
-        measured = {c for fcl in self.clbits for c in fcl}
-        return float(p.mean()) * 2.0 ** sum(1 for c in cl if int(c) in measured) - 1.0
+        return float(p.mean()) * 2.0 ** self._measured_among(clbits) - 1.0
 
     def fidelity_to_counts(self, counts: dict, clbits=None) -> float:
         """Hellinger fidelity between the knit and a counts dict ``{key: count}`` (shots of an uncut run or
@@ -1228,7 +1278,7 @@ class KnitReducer:
 
     def _expectation_fused(self, masks) -> np.ndarray:
         self.ctx.bind_stream()
-        on_device = type(masks).__module__.split(".")[0] == "torch" and masks.is_cuda
+        on_device = _is_tensor(masks) and masks.is_cuda
         ks = keys_array(masks, self.N) if on_device else masks_array(masks, self.N)  # device masks stay there
         if not self.frags:
             return np.full(len(ks), self._scalar) if len(ks) else np.zeros(0)
@@ -1260,9 +1310,7 @@ class KnitReducer:
                                   T.from_numpy(np.ascontiguousarray(coefs, dtype=np.float64)).to(dev)))
             self._moment_specs = specs
         keep, _ = split_clbits(cl, self.clbits)
-        rows = [q if kp == (1 << len(fcl)) - 1 else engine.reduce_bits(self.ctx, q, len(fcl), kp, [0])
-                for q, fcl, kp in zip(self.qs, self.clbits, keep)]
-        return rows, self._moment_specs, self.clbits, self.ops.num_terms
+        return self._reduced(keep), self._moment_specs, self.clbits, self.ops.num_terms
 
     def overlap(self, other=None, clbits=None) -> float:
         """``sum_y R_S[y] R'_S[y]``: the overlap of this knit's marginal onto ``clbits`` (``None``: all clbits)
@@ -1278,13 +1326,8 @@ class KnitReducer:
         self.ctx.bind_stream()
         same = other is None or other is self
         if not same:
-            if not isinstance(other, KnitReducer):
-                raise ValueError("other must be a KnitReducer or None")
-            if other.N != self.N:
-                raise ValueError(f"{self.N} clbits against {other.N}")
-            if other.device != self.device:
-                raise ValueError(f"reducers on devices {self.device} and {other.device}")
-        cl = list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+            self._check_other(other)
+        cl = self._clbits(clbits)
         return overlap_of_sides(self.ctx, self._moment_sides(cl), None if same else other._moment_sides(cl), cl)
 
     def collision_probability(self, clbits=None) -> float:
@@ -1301,9 +1344,7 @@ class KnitReducer:
     def ideal_xeb(self, clbits=None) -> float:
         """The linear XEB score an ideal sampler of this knit would reach in expectation:
         ``D * sum_y R_S[y]^2 - 1`` with ``D`` as in :meth:`linear_xeb`; about 1 for a Porter-Thomas output."""
-        cl = range(self.N) if clbits is None else clbits
-        measured = {c for fcl in self.clbits for c in fcl}
-        return self.collision_probability(clbits) * 2.0 ** sum(1 for c in cl if int(c) in measured) - 1.0
+        return self.collision_probability(clbits) * 2.0 ** self._measured_among(clbits) - 1.0
 
     def l2_distance(self, other, clbits=None) -> float:
         """``||R_S - R'_S||_2 = sqrt(max(s_aa - 2 s_ab + s_bb, 0))`` from three overlaps. The three sums cancel:
@@ -1320,43 +1361,25 @@ class KnitReducer:
         return self.renyi2_entropy(a) + self.renyi2_entropy(b) - self.renyi2_entropy(a + b)
 
     # -- nonlinear functionals: the streamed scan ------------------------------------------------
-    def _scan_operands(self, cl: list, other=None) -> tuple:
-        """``(A, B, where_a, where_b, A2, B2)``: the two sides of the scan of the marginal onto ``cl``
-        (:func:`scan_sides` of the fragments' kept widths; a side is the Khatri-Rao product of its fragments'
-        reduced operands) and, per side, the key bit of every bit of its index. ``other``: the same sides of another
-        reducer's knit, its fragments paired by :func:`match_fragments` and permuted to this one's bit order."""
+    def _scan_operands(self, cl: list, other=None) -> ScanSides:
+        """The two sides of the scan of the marginal onto ``cl`` (:func:`scan_sides` of the fragments' kept widths).
+        ``other``: also the same sides of another reducer's knit, its fragments paired by :func:`match_fragments` and
+        permuted to this one's bit order."""
         T = engine.torch()
         dev = T.device("cuda", self.device)
-        if not self.frags:
-            mats, where, K = [T.full((1, 1), self._scalar, dtype=T.float64, device=dev)], [[]], 1
-        else:
-            keep, where = key_positions(cl, self.clbits)
-            mats, K = self._operands(keep, [[0]] * len(keep)), self.ops.num_terms
+        mats, where, K = self._keyed_operands(cl)
         sa, sb = scan_sides([len(w) for w in where])
-        A = _side_operand(self.ctx, [mats[f] for f in sa], K, dev)
-        B = _side_operand(self.ctx, [mats[f] for f in sb], K, dev)
-        wa, wb = [b for f in sa for b in where[f]], [b for f in sb for b in where[f]]
+        sides = ScanSides(A=_side_operand(self.ctx, [mats[f] for f in sa], K, dev),
+                          B=_side_operand(self.ctx, [mats[f] for f in sb], K, dev),
+                          where_a=[b for f in sa for b in where[f]], where_b=[b for f in sb for b in where[f]])
         if other is None:
-            return A, B, wa, wb, None, None
+            return sides
         pairs, _, only_o = match_fragments(self.clbits if self.frags else [[]], other.clbits if other.frags else [[]], cl)
-        if not other.frags:
-            omats, K2 = [T.full((1, 1), other._scalar, dtype=T.float64, device=dev)], 1
-        else:
-            okeep, _ = key_positions(cl, other.clbits)
-            omats, K2 = other._operands(okeep, [[0]] * len(okeep)), other.ops.num_terms
+        omats, _, K2 = other._keyed_operands(cl)
         partner = {f: _permute_bits(T, omats[g], order) for f, g, order in pairs}
         extra = [omats[g] for g in only_o]  # no kept clbit: they scale side A
-        A2 = _side_operand(self.ctx, [partner[f] for f in sa if f in partner] + extra, K2, dev)
-        B2 = _side_operand(self.ctx, [partner[f] for f in sb if f in partner], K2, dev)
-        return A, B, wa, wb, A2, B2
-
-    @staticmethod
-    def _scan_key(flat, mb: int, wa: list, wb: list):
-        """Flat scan indices ``i << mb | j`` (an int or an int64 tensor) as keys."""
-        return deposit_bits(deposit_bits(flat & 0, flat >> mb, wa), flat & ((1 << mb) - 1), wb)
-
-    def _scan_clbits(self, clbits) -> list:
-        return list(range(self.N)) if clbits is None else check_clbits(clbits, self.N)
+        return sides._replace(A2=_side_operand(self.ctx, [partner[f] for f in sa if f in partner] + extra, K2, dev),
+                              B2=_side_operand(self.ctx, [partner[f] for f in sb if f in partner], K2, dev))
 
     def scan(self, clbits=None, *, threshold: float = 0.0, entropy: bool = True) -> KnitScan:
         """Statistics of the exact knit ``R`` (``clbits``: of its marginal onto them, bit ``i`` of a key =
@@ -1367,22 +1390,23 @@ class KnitReducer:
         exact zeros: they are not scanned but enter ``min`` / ``max`` / ``count_above`` as such. Deterministic: two
         calls return the same values."""
         self.ctx.bind_stream()
-        cl = self._scan_clbits(clbits)
-        A, B, wa, wb, _, _ = self._scan_operands(cl)
-        st = engine.knit_scan(self.ctx, A, B, tau=threshold, entropy=entropy, hist=True)
-        mb, P = len(wb), st["pos"]
+        cl = self._clbits(clbits)
+        sides = self._scan_operands(cl)
+        st = engine.knit_scan(self.ctx, sides.A, sides.B, tau=threshold, entropy=entropy, hist=True)
+        P = st["pos"]
         H = (st["ent"] / P + np.log(P)) / np.log(2.0) if entropy and P > 0 else float("nan")
         # key bits that no fragment measures: every key with one of them set holds an exact zero
-        dead = [b for b in range(len(cl)) if b not in wa and b not in wb]
+        scanned = sides.where_a + sides.where_b
+        dead = [b for b in range(len(cl)) if b not in scanned]
         if dead:
             zero_key = 1 << dead[0]  # the lowest such key
             if threshold < 0:
-                st["count_tau"] += ((1 << len(dead)) - 1) << (len(wa) + len(wb))
+                st["count_tau"] += ((1 << len(dead)) - 1) << len(scanned)
             if st["max"] < 0:
                 st["max"], st["argmax"] = 0.0, None
             if st["min"] > 0:
                 st["min"], st["argmin"] = 0.0, None
-        key = lambda flat: zero_key if flat is None else int(self._scan_key(flat, mb, wa, wb))
+        key = lambda flat: zero_key if flat is None else int(sides.key(flat))
         return KnitScan(mass=st["sum"], l1=st["abs"], positive_mass=P, negativity=(st["abs"] - st["sum"]) / 2,
                         collision=st["sq"], shannon_entropy=float(H), max=st["max"],
                         argmax=key(st["argmax"]), min=st["min"],
@@ -1402,54 +1426,55 @@ class KnitReducer:
         sc = self.scan(clbits, entropy=False)
         return sc.argmax, sc.max
 
-    def _collect_sorted(self, A, B, wa: list, wb: list, tau: float, capacity: int):
+    def _collect_sorted(self, sides: ScanSides, tau: float, capacity: int):
         T = engine.torch()
-        idx, vals, count = engine.knit_collect(self.ctx, A, B, tau, capacity)
+        idx, vals, count = engine.knit_collect(self.ctx, sides.A, sides.B, tau, capacity)
         if count > capacity:
             raise ValueError(f"{count} outcomes above {tau!r}, more than capacity = {capacity}")
-        keys = self._scan_key(idx, len(wb), wa, wb)
-        keys, by_key = T.sort(keys)
+        keys, by_key = T.sort(sides.key(idx))
         vals, by_val = T.sort(vals[by_key], descending=True, stable=True)  # ties stay in key order
         return keys[by_val], vals
+
+    def _outputs_above(self, tau: float, cl: list, capacity: int) -> tuple:
+        """What :meth:`heavy_outputs` and :meth:`projected_heavy_outputs` share: the sorted outcomes above ``tau``."""
+        self.ctx.bind_stream()
+        return self._collect_sorted(self._scan_operands(cl), tau, int(capacity))
+
+    def _largest(self, k: int, cl: list, capacity: int, lower: float = 0.0, above_lower: int = 0) -> tuple:
+        """What :meth:`top_k` and :meth:`projected_top_k` share: the ``k`` largest outcomes above ``lower``, of which
+        there are ``above_lower``. The histogram's threshold is never negative, so :meth:`top_k`'s ``lower = 0`` never
+        replaces it."""
+        self.ctx.bind_stream()
+        k = check_not_negative("k", k)
+        sides = self._scan_operands(cl)
+        st = engine.knit_scan(self.ctx, sides.A, sides.B, hist=True)
+        tau, count = histogram_threshold(st["hist"], k)
+        if tau < lower:
+            tau, count = lower, above_lower
+        if count > capacity:
+            raise ValueError(f"{count} outcomes share the binades of the top {k}, more than capacity = {capacity}")
+        keys, vals = self._collect_sorted(sides, tau, count)
+        return keys[:k], vals[:k]
 
     def heavy_outputs(self, threshold: float, clbits=None, capacity: int = 1 << 24) -> tuple:
         """Device ``(keys int64, values float64)`` of every outcome with ``R_S > threshold`` (strict), sorted by
         value descending, ties by key ascending (``qk_knit_collect``). ``threshold >= 0``: a key on a clbit that no
         fragment measures holds a zero and is never listed. ``ValueError``, naming the count, when more than
         ``capacity`` outcomes qualify."""
-        if not float(threshold) >= 0:
-            raise ValueError(f"threshold must not be negative, not {threshold}")
-        self.ctx.bind_stream()
-        A, B, wa, wb, _, _ = self._scan_operands(self._scan_clbits(clbits))
-        return self._collect_sorted(A, B, wa, wb, float(threshold), int(capacity))
+        return self._outputs_above(check_not_negative("threshold", threshold, float), self._clbits(clbits), capacity)
 
     def top_k(self, k: int, clbits=None, capacity: int = 1 << 24) -> tuple:
         """Device ``(keys, values)`` of the ``k`` most probable outcomes (fewer when fewer are positive), sorted as
         :meth:`heavy_outputs`: one scan with the histogram, then :func:`histogram_threshold` gives a threshold whose
         count is known before anything is collected. ``ValueError``, naming the count, when the binade that holds
         the ``k``-th value makes that count exceed ``capacity`` (a uniform output, say)."""
-        self.ctx.bind_stream()
-        k = int(k)
-        if k < 0:
-            raise ValueError(f"k must not be negative, not {k}")
-        A, B, wa, wb, _, _ = self._scan_operands(self._scan_clbits(clbits))
-        st = engine.knit_scan(self.ctx, A, B, hist=True)
-        tau, count = histogram_threshold(st["hist"], k)
-        if count > capacity:
-            raise ValueError(f"{count} outcomes share the binades of the top {k}, more than capacity = {capacity}")
-        keys, vals = self._collect_sorted(A, B, wa, wb, tau, count)
-        return keys[:k], vals[:k]
+        return self._largest(k, self._clbits(clbits), capacity)
 
     def _pair_scan(self, other, clbits) -> dict:
-        if not isinstance(other, KnitReducer):
-            raise ValueError("other must be a KnitReducer")
-        if other.N != self.N:
-            raise ValueError(f"{self.N} clbits against {other.N}")
-        if other.device != self.device:
-            raise ValueError(f"reducers on devices {self.device} and {other.device}")
+        self._check_other(other)
         self.ctx.bind_stream()
-        A, B, _, _, A2, B2 = self._scan_operands(self._scan_clbits(clbits), other)
-        return engine.knit_scan(self.ctx, A, B, A2, B2)
+        sides = self._scan_operands(self._clbits(clbits), other)
+        return engine.knit_scan(self.ctx, sides.A, sides.B, sides.A2, sides.B2)
 
     def hellinger_fidelity(self, other, clbits=None) -> float:
         """The Hellinger fidelity ``(sum sqrt(p q))^2 / (sum p sum q)`` of ``p = max(R_S, 0)`` and
@@ -1475,13 +1500,13 @@ class KnitReducer:
         "Nearest probability distribution"). Keys on clbits that no fragment measures hold exact zeros and are never
         members. With no fragment at all there is one outcome at key 0."""
         self.ctx.bind_stream()
-        cl = self._scan_clbits(clbits)
+        cl = self._clbits(clbits)
         _, _, accuracy = engine.check_projection_args(0.0, 0.0, accuracy)
-        A, B, _, _, _, _ = self._scan_operands(cl)
+        sides = self._scan_operands(cl)
         seen = {}
 
         def evaluate(theta):
-            seen.update(engine.knit_project_scan(self.ctx, A, B, theta=theta, accuracy=accuracy))
+            seen.update(engine.knit_project_scan(self.ctx, sides.A, sides.B, theta=theta, accuracy=accuracy))
             return seen["msum"], seen["tsum"], seen["nkept"]
 
         th = projection_threshold(evaluate, max_passes)
@@ -1509,12 +1534,12 @@ class KnitReducer:
         ``entropy``, one more launch of the mainloop for the logarithms)."""
         self._check_projection(projection)
         self.ctx.bind_stream()
-        A, B, wa, wb, _, _ = self._scan_operands(projection.clbits)
-        st = engine.knit_project_scan(self.ctx, A, B, theta=projection.theta, accuracy=projection.accuracy,
+        sides = self._scan_operands(projection.clbits)
+        st = engine.knit_project_scan(self.ctx, sides.A, sides.B, theta=projection.theta, accuracy=projection.accuracy,
                                       entropy=entropy)
         P = st["psum"]
         H = (st["pent"] / P + np.log(P)) / np.log(2.0) if entropy and st["nkept"] and P > 0 else float("nan")
-        key = int(self._scan_key(st["argmax"], len(wb), wa, wb)) if st["nkept"] else None
+        key = int(sides.key(st["argmax"])) if st["nkept"] else None
         return ProjectedScan(mass=P, collision=st["psq"], shannon_entropy=float(H), max=st["pmax"], argmax=key,
                              support=st["nkept"])
 
@@ -1525,11 +1550,8 @@ class KnitReducer:
         ``max(theta, accuracy, theta + min_value)``, then the shift. ``ValueError``, naming the count, when more
         than ``capacity`` entries qualify."""
         lower = self._check_projection(projection)
-        if not float(min_value) >= 0:
-            raise ValueError(f"min_value must not be negative, not {min_value}")
-        self.ctx.bind_stream()
-        A, B, wa, wb, _, _ = self._scan_operands(projection.clbits)
-        keys, vals = self._collect_sorted(A, B, wa, wb, max(lower, projection.theta + float(min_value)), int(capacity))
+        tau = max(lower, projection.theta + check_not_negative("min_value", min_value, float))
+        keys, vals = self._outputs_above(tau, projection.clbits, capacity)
         return keys, vals - projection.theta
 
     def projected_top_k(self, k: int, projection: KnitProjection, capacity: int = 1 << 24) -> tuple:
@@ -1537,19 +1559,8 @@ class KnitReducer:
         sorted as :meth:`heavy_outputs`: the route of :meth:`top_k` with its threshold raised to the kept set's
         (the shift leaves the order of the entries as it is)."""
         lower = self._check_projection(projection)
-        self.ctx.bind_stream()
-        k = int(k)
-        if k < 0:
-            raise ValueError(f"k must not be negative, not {k}")
-        A, B, wa, wb, _, _ = self._scan_operands(projection.clbits)
-        st = engine.knit_scan(self.ctx, A, B, hist=True)
-        tau, count = histogram_threshold(st["hist"], k)
-        if tau < lower:
-            tau, count = lower, projection.kept
-        if count > capacity:
-            raise ValueError(f"{count} outcomes share the binades of the top {k}, more than capacity = {capacity}")
-        keys, vals = self._collect_sorted(A, B, wa, wb, tau, count)
-        return keys[:k], vals[:k] - projection.theta
+        keys, vals = self._largest(k, projection.clbits, capacity, lower, projection.kept)
+        return keys, vals - projection.theta
 
     def _projected_pair_scan(self, other, projection, other_projection, clbits) -> dict:
         self._check_projection(projection)
@@ -1561,16 +1572,11 @@ class KnitReducer:
         if projection.accuracy != other_projection.accuracy:
             raise ValueError(f"the projections were truncated at {projection.accuracy} and "
                              f"{other_projection.accuracy}: one pass takes one accuracy")
-        if not isinstance(other, KnitReducer):
-            raise ValueError("other must be a KnitReducer")
-        if other.N != self.N:
-            raise ValueError(f"{self.N} clbits against {other.N}")
-        if other.device != self.device:
-            raise ValueError(f"reducers on devices {self.device} and {other.device}")
+        self._check_other(other)
         self.ctx.bind_stream()
-        A, B, _, _, A2, B2 = self._scan_operands(cl, other)
-        return engine.knit_project_scan(self.ctx, A, B, A2, B2, theta=projection.theta, theta2=other_projection.theta,
-                                        accuracy=projection.accuracy)
+        sides = self._scan_operands(cl, other)
+        return engine.knit_project_scan(self.ctx, sides.A, sides.B, sides.A2, sides.B2, theta=projection.theta,
+                                        theta2=other_projection.theta, accuracy=projection.accuracy)
 
     def projected_hellinger_fidelity(self, other, projection: KnitProjection, other_projection: KnitProjection,
                                      clbits=None) -> float:
@@ -1615,19 +1621,17 @@ class KnitReducer:
         out = np.zeros(len(zs))
         if not len(zs):
             return out
-        A, B, wa, wb, _, _ = self._scan_operands(cl)
+        sides = self._scan_operands(cl)
         side = lambda z, w: sum(1 << i for i, b in enumerate(w) if z >> cl[b] & 1)
-        pairs = [(side(int(z), wa), side(int(z), wb)) for z in zs]
-        ma, mb = len(wa), len(wb)
+        pairs = [(side(int(z), sides.where_a), side(int(z), sides.where_b)) for z in zs]
+        ma, mb = len(sides.where_a), len(sides.where_b)
         tiles = sum(scan_shape(ma, mb, i0, i1)["tiles"] for i0, i1 in engine.scan_slabs(ma, mb))
         per = max(1, min(PROJ_TILE_MASKS, PROJ_TILE_BYTES // (8 * tiles)))
         for c0 in range(0, len(pairs), per):
             chunk = pairs[c0:c0 + per]
-            sums = [T.stack([W[m].sum() for m in range(len(chunk))]) for W in self._tile_masses(A, B, projection, chunk)]
-            acc = np.zeros(len(chunk))
-            for s in T.stack(sums).cpu().numpy():  # ascending slabs
-                acc = acc + s
-            out[c0:c0 + len(chunk)] = acc
+            sums = [T.stack([W[m].sum() for m in range(len(chunk))])
+                    for W in self._tile_masses(sides.A, sides.B, projection, chunk)]
+            out[c0:c0 + len(chunk)] = engine.sum_slabs(T.stack(sums).cpu().numpy())
         return out
 
     def projected_marginal(self, clbits, projection: KnitProjection, *, route: str | None = None):
@@ -1650,7 +1654,8 @@ class KnitReducer:
         if route not in (None, "tile", "mask"):
             raise ValueError(f"route must be None, 'tile' or 'mask', not {route!r}")
         k = len(cl)
-        A, B, wa, wb, _, _ = self._scan_operands(pcl)
+        sides = self._scan_operands(pcl)
+        A, B, wa, wb = sides.A, sides.B, sides.where_a, sides.where_b
         ma, mb = len(wa), len(wb)
         want = {pcl.index(c): i for i, c in enumerate(cl)}  # key bit of the projection -> bit of the result
         ka, kb = [i for i, b in enumerate(wa) if b in want], [i for i, b in enumerate(wb) if b in want]
@@ -1696,15 +1701,12 @@ class KnitReducer:
         self.ctx.bind_stream()
         T = engine.torch()
         dev = T.device("cuda", self.device)
-        shots = int(shots)
-        if shots < 0:
-            raise ValueError(f"shots must not be negative, not {shots}")
+        shots = check_not_negative("shots", shots)
         if shots == 0:
             return T.zeros(0, dtype=T.int64, device=dev)
-        cl = list(projection.clbits)
-        A, B, wa, wb, _, _ = self._scan_operands(cl)
-        ma, mb = len(wa), len(wb)
-        slabs = engine.scan_slabs(ma, mb)
+        sides = self._scan_operands(list(projection.clbits))
+        A, B = sides.A, sides.B
+        slabs = engine.scan_slabs(len(sides.where_a), len(sides.where_b))
         Ws = [W[0] for W in self._tile_masses(A, B, projection, [(0, 0)])]
         u = engine.uniforms(self.ctx, seed, PROJ_DRAW_LABEL, 0, shots)
         draw = lambda s, us: engine.knit_project_draw(self.ctx, A, B, projection.theta, projection.accuracy, Ws[s], us,
@@ -1729,7 +1731,7 @@ class KnitReducer:
                 flat[sel] = draw(s, us.contiguous())[0]
         if bool((flat < 0).any()):
             raise RuntimeError("the projection is empty: nothing to draw from")
-        return self._scan_key(flat, mb, wa, wb)
+        return sides.key(flat)
 
     def marginal_parity(self, clbits, masks):
         """The mixed form: device fp64 ``[M, 2^k]``, row j the marginal onto ``clbits`` of

@@ -231,7 +231,8 @@ def test_lookup_entries_reject_bad_arguments(T):
         args.update(kw)
         with pytest.raises(ValueError):
             engine.knit_at(ctx, args.pop("Xts"), args.pop("positions"), args.pop("keys"), **args)
-    for bad_x in (X.float(), X[0], T.ones((2, 6), dtype=T.float64, device="cuda"), X.cpu()):
+    for bad_x in (X.float(), X[0], T.ones((2, 6), dtype=T.float64, device="cuda"), X.cpu(),
+                  T.ones((2, 8), dtype=T.float64, device="cuda")[:, ::2]):  # the last: column stride 2
         with pytest.raises(ValueError):
             engine.transpose_rows(ctx, bad_x)
     with pytest.raises(ValueError):

@@ -211,6 +211,7 @@ def test_gram_rows_rejects_bad_arguments(T):
     out = T.full((4, 3), -7.0, dtype=T.float64, device="cuda")
     for kw in (dict(m=31), dict(m=4), dict(A=A.float()), dict(B=B.float()), dict(A=A.cpu()), dict(B=B.cpu()), dict(A=A[0]),
                dict(A=A.T), dict(A=T.ones((4, 6), dtype=T.float64, device="cuda"), m=None), dict(A=A[:0]),
+               dict(A=A.view(-1).as_strided((4, 8), (4, 1))),  # rows 4 doubles apart: below 2^m
                dict(out=out.float()), dict(out=out.cpu()), dict(out=out[:3]), dict(out=out.T), dict(out=A[:, :3]),
                dict(out=T.full((3, 4), -7.0, dtype=T.float64, device="cuda").T)):
         args = dict(A=A, B=B, m=3, out=out)

@@ -260,6 +260,9 @@ def test_reduce_bits_rejects_bad_masks_before_touching_a_device():
         engine.reduce_bits(None, None, 31, 0, [0])
     with pytest.raises(ValueError, match="at least one"):
         engine.reduce_bits(None, None, 4, 0, [])
+    overlapping_rows = engine.torch().ones(32, dtype=engine.torch().float64).as_strided((2, 16), (8, 1))
+    with pytest.raises(ValueError, match="row stride"):
+        engine.reduce_bits(None, overlapping_rows, 4, 0, [0])
     with pytest.raises(ValueError):
         ob.reduce_bits_host(np.zeros((1, 16)), 4, 0b0011, [0b0010])
 

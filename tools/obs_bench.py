@@ -411,7 +411,8 @@ def scan_leg(args):
     ctx = engine.get_context(0)
     res["fragments"] = [{"rows": int(q.shape[0]), "m": len(cl)} for q, cl in zip(red.qs, red.clbits)]
     K = res["terms"] = int(red.ops.num_terms)
-    A, B, wa, wb, _, _ = red._scan_operands(list(range(red.N)))
+    sides = red._scan_operands(list(range(red.N)))
+    A, B, wa, wb = sides.A, sides.B, sides.where_a, sides.where_b
     res["sides"] = {"bits_a": len(wa), "bits_b": len(wb)}
     flops = 2.0 * K * 2.0 ** (len(wa) + len(wb))
     for name, knits, fn in (("plain", 1, lambda: engine.knit_scan(ctx, A, B)),
@@ -589,7 +590,8 @@ def projection_leg(args):
     red = base.with_readout_mitigation(conf)
     ctx = engine.get_context(0)
     K = res["terms"] = int(red.ops.num_terms)
-    A, B, wa, wb, _, _ = red._scan_operands(list(range(red.N)))
+    sides = red._scan_operands(list(range(red.N)))
+    A, B, wa, wb = sides.A, sides.B, sides.where_a, sides.where_b
     res["sides"] = {"bits_a": len(wa), "bits_b": len(wb)}
     theta = red.project().theta
     legs = {"qk_knit_scan_plain": lambda: engine.knit_scan(ctx, A, B),
@@ -701,7 +703,8 @@ def projected_leg(args):
     red = KnitReducer(virt).with_readout_mitigation(conf)
     ctx = engine.get_context(0)
     res["terms"] = K = int(red.ops.num_terms)
-    A, B, wa, wb, _, _ = red._scan_operands(list(range(red.N)))
+    sides = red._scan_operands(list(range(red.N)))
+    A, B, wa, wb = sides.A, sides.B, sides.where_a, sides.where_b
     res["sides"] = {"bits_a": len(wa), "bits_b": len(wb)}
     pr = red.project()
     theta = pr.theta
