@@ -11,7 +11,7 @@ plus the circuit IR (:mod:`.circuit`), the benchmark generators and cut-spec
 builder (:mod:`.generators`, :mod:`.cutting`) and the engine (:mod:`.engine`,
 C ABI in ``include/qknit.h``).
 """
-from .circuit import ClassicalRegister, QuantumCircuit, QuantumRegister
+from .circuit import ClassicalRegister, Parameter, QuantumCircuit, QuantumRegister
 from .quasi_distr import QuasiDistr
 from .virtual_gates import (
     RZZ_ACCURACY,
@@ -32,6 +32,7 @@ from .run import (RunTimeInfo, run_virtual_circuit, run_virtual_circuit_collisio
                   run_virtual_circuit_npd,
                   run_virtual_circuit_overlap, run_virtual_circuit_probabilities, run_virtual_circuit_scan,
                   run_virtual_circuit_shots, run_virtual_circuit_top_k, run_virtual_circuit_xeb)
+from .parametric import ParametricKnit
 
 __all__ = [
     "ClassicalRegister", "QuantumCircuit", "QuantumRegister", "QuasiDistr", "RZZ_ACCURACY",
@@ -41,5 +42,5 @@ __all__ = [
     "run_virtual_circuit_marginal", "run_virtual_circuit_expectation", "run_virtual_circuit_shots",
     "run_virtual_circuit_probabilities", "run_virtual_circuit_xeb", "run_virtual_circuit_collision",
     "run_virtual_circuit_overlap", "run_virtual_circuit_scan", "run_virtual_circuit_top_k",
-    "run_virtual_circuit_fidelity", "run_virtual_circuit_npd",
+    "run_virtual_circuit_fidelity", "run_virtual_circuit_npd", "Parameter", "ParametricKnit",
 ]

@@ -71,6 +71,10 @@ SIGNATURES = {
                                         c_vp, c_vp, c_lp, c_vp, c_vp]),
     "qk_sweep_compiled_multi_shared": (c_i32, [c_vp, c_vp, ctypes.c_int, ctypes.POINTER(QkProgram), c_lp, c_vp, c_vp,
                                                c_lp, c_vp, c_vp, c_lp, c_vp, c_vp, c_lp, c_vp, c_vp]),
+    "qk_sweep_bound_workspace_bytes": (c_i32, [ctypes.POINTER(QkProgram), c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "qk_sweep_bound_check": (c_i32, [ctypes.POINTER(QkProgram), c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
+    "qk_sweep_bound": (c_i32, [c_vp, c_vp, ctypes.POINTER(QkProgram), c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp,
+                               c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "qk_reduce_labels": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "qk_gemm_keyed": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_i64, c_vp, ctypes.c_int]),

@@ -26,6 +26,119 @@ from . import gates as _g
 _reg_counter = itertools.count()
 
 
+class ParameterExpression:
+    """An affine expression ``const + sum_i coef_i * p_i`` of :class:`Parameter` s: what a
+    rotation gate holds in place of an angle until :meth:`QuantumCircuit.bind` (or the run-time
+    binding table of a parametric sweep) gives the parameters their values. Formed by ``+``, ``-``,
+    unary ``-``, and ``*`` / ``/`` with a float; nothing else is defined."""
+
+    __slots__ = ("const", "terms")
+
+    def __init__(self, const: float = 0.0, terms: dict | None = None):
+        self.const = float(const)
+        self.terms = dict(terms or {})  # Parameter -> coefficient, in order of first appearance
+
+    @property
+    def parameters(self) -> list:
+        return list(self.terms)
+
+    @property
+    def parameter_names(self) -> list:
+        return [p.name for p in self.terms]
+
+    @staticmethod
+    def _number(x) -> bool:
+        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+    def _combine(self, other, sign: float):
+        if isinstance(other, ParameterExpression):
+            terms = dict(self.terms)
+            for p, c in other.terms.items():
+                terms[p] = terms.get(p, 0.0) + sign * c
+            return ParameterExpression(self.const + sign * other.const, terms)
+        if self._number(other):
+            return ParameterExpression(self.const + sign * float(other), self.terms)
+        return NotImplemented
+
+    def __add__(self, other):
+        return self._combine(other, 1.0)
+
+    __radd__ = __add__
+
+    def __sub__(self, other):
+        return self._combine(other, -1.0)
+
+    def __rsub__(self, other):
+        return (-self)._combine(other, 1.0)
+
+    def __neg__(self):
+        return ParameterExpression(-self.const, {p: -c for p, c in self.terms.items()})
+
+    def __pos__(self):
+        return self
+
+    def __mul__(self, other):
+        if not self._number(other):
+            return NotImplemented
+        k = float(other)
+        return ParameterExpression(self.const * k, {p: c * k for p, c in self.terms.items()})
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, other):
+        if not self._number(other):
+            return NotImplemented
+        k = float(other)
+        return ParameterExpression(self.const / k, {p: c / k for p, c in self.terms.items()})
+
+    def evaluate(self, values: dict) -> float:
+        """The value with every parameter taken from the mapping ``values`` (``Parameter`` -> float)."""
+        out = self.const
+        for p, c in self.terms.items():
+            if p not in values:
+                raise ValueError(f"no value for parameter '{p.name}'")
+            out += c * float(values[p])
+        return out
+
+    def evaluate_batch(self, values: np.ndarray, column: dict) -> np.ndarray:
+        """``[B]`` values for the rows of ``values [B, P]``; ``column`` maps a parameter to its column."""
+        out = np.full(values.shape[0], self.const, dtype=np.float64)
+        for p, c in self.terms.items():
+            if p not in column:
+                raise ValueError(f"no value for parameter '{p.name}'")
+            out += c * values[:, column[p]]
+        return out
+
+    def structure(self, index: dict) -> tuple:
+        """The expression with each parameter replaced by ``index[parameter]``: equal for two circuits
+        of one structure whose parameters are different objects."""
+        return ("expr", self.const, tuple((index[p], c) for p, c in self.terms.items()))
+
+    def __repr__(self) -> str:
+        parts = [f"{c:.6g}*{p.name}" for p, c in self.terms.items()]
+        if self.const != 0.0 or not parts:
+            parts.append(f"{self.const:.6g}")
+        return " + ".join(parts)
+
+
+class Parameter(ParameterExpression):
+    """A named run-time parameter. Equality and hash are by identity; the name is for messages only."""
+
+    __slots__ = ("name",)
+
+    def __init__(self, name: str):
+        self.name = str(name)
+        super().__init__(0.0, {self: 1.0})
+
+    def __repr__(self) -> str:
+        return self.name
+
+
+def is_parametric(op) -> bool:
+    """Whether an operation still holds a :class:`ParameterExpression` among its parameters."""
+    return any(isinstance(p, ParameterExpression) for p in getattr(op, "params", ()) or ())
+
+
 class Bit:
     __slots__ = ("_register", "_index")
 
@@ -117,7 +230,8 @@ class Operation:
         return _g.gate_matrix(self.name, self.params)
 
     def __repr__(self) -> str:
-        p = f"({', '.join(f'{x:.6g}' for x in self.params)})" if self.params else ""
+        p = (f"({', '.join(repr(x) if isinstance(x, ParameterExpression) else f'{x:.6g}' for x in self.params)})"
+             if self.params else "")
         return f"{self.name}{p}"
 
 
@@ -328,6 +442,7 @@ class QuantumCircuit:
     cz = _std_gate("cz", 2)
     ch = _std_gate("ch", 2)
     cp = _std_gate("cp", 2)
+    cu1 = _std_gate("cu1", 2)
     crz = _std_gate("crz", 2)
     crx = _std_gate("crx", 2)
     cry = _std_gate("cry", 2)
@@ -355,6 +470,58 @@ class QuantumCircuit:
         for i, q in enumerate(self._qubits):
             self.append(Measure(), [q], [creg[i]])
         return self
+
+    # ------------------------------------------------------------------ parameters
+    @property
+    def parameters(self) -> list:
+        """The distinct :class:`Parameter` s of the circuit's gates, in order of first appearance
+        (composite instructions included)."""
+        seen: dict = {}
+        for instr in self._data:
+            op = instr.operation
+            if isinstance(op, CompositeInstruction):
+                for p in op.definition.parameters:
+                    seen.setdefault(p, None)
+            for x in getattr(op, "params", ()) or ():
+                if isinstance(x, ParameterExpression):
+                    for p in x.terms:
+                        seen.setdefault(p, None)
+        return list(seen)
+
+    def _binding(self, values) -> dict:
+        params = self.parameters
+        if isinstance(values, dict):
+            surplus = [p for p in values if p not in set(params)]
+            if surplus:
+                raise ValueError(f"values for parameters the circuit does not hold: {[getattr(p, 'name', p) for p in surplus]}")
+            missing = [p.name for p in params if p not in values]
+            if missing:
+                raise ValueError(f"no value for parameters {missing}")
+            return {p: float(values[p]) for p in params}
+        vals = [float(v) for v in np.asarray(values, dtype=np.float64).reshape(-1)]
+        if len(vals) != len(params):
+            raise ValueError(f"{len(params)} parameters but {len(vals)} values")
+        return dict(zip(params, vals))
+
+    def bind(self, values) -> "QuantumCircuit":
+        """A new circuit with every expression evaluated to a float. ``values``: a sequence in
+        :attr:`parameters` order, or a mapping from ``Parameter`` to float; a missing or surplus value
+        is a ``ValueError``. Every other instruction (virtual gates, measures, barriers) and the
+        registers are shared with this circuit as they are."""
+        return self._bound(self._binding(values))
+
+    def _bound(self, binding: dict) -> "QuantumCircuit":
+        new = QuantumCircuit(*self.qregs, *self.cregs, name=self.name)
+        for instr in self._data:
+            op = instr.operation
+            if isinstance(op, CompositeInstruction) and op.definition.parameters:
+                new._data.append(instr.replace(operation=CompositeInstruction(op.definition._bound(binding), op.name)))
+            elif is_parametric(op):
+                params = [x.evaluate(binding) if isinstance(x, ParameterExpression) else x for x in op.params]
+                new._data.append(instr.replace(operation=Gate(op.name, op.num_qubits, params, op.label)))
+            else:
+                new._data.append(instr)
+        return new
 
     # ------------------------------------------------------------------ transforms
     def copy(self) -> "QuantumCircuit":

@@ -207,6 +207,10 @@ struct SweepArgs {
     int flags;
     uint32_t traced_local;
     int n, n_eff, m, n_slots;
+    // bound sweep (BOUND kernels only): n_jobs counts units u = b * jobs_per_binding + j
+    const double* bind_mats;  // [n_bind][n_params][8]
+    int64_t jobs_per_binding;
+    int n_params;
 };
 
 // Deposit the low bits of `x` into the set bits of `mask` (mask has <= 64 bits).
@@ -223,7 +227,10 @@ __device__ __forceinline__ uint64_t pdep64(uint64_t x, uint64_t mask) {
 
 // One pass of the batched sweep. PACKED: a tile = 2^(12-n_eff) whole jobs. SPLIT: a tile =
 // 12 state bits (tile_mask) of one job, 2^(n-12) tiles per job.
-template <bool PACKED>
+// BOUND (qk_sweep_bound): a job index is a unit u = b * jobs_per_binding + j. Slot matrices and the sign
+// are read by j, QK_PARAM matrices from binding b's table, state and output rows by u. In a PACKED tile
+// bindings share the tile, so b is per lane like the job; padded tile slots reuse the last valid unit.
+template <bool PACKED, bool BOUND>
 // The program (ops, groups, mats) comes in as separate __restrict__ read-only pointers so the
 // compiler can prove it uniform and unclobbered: it then uses scalar (K$) loads instead of a
 // vector-memory round trip per op.
@@ -334,6 +341,11 @@ __global__ __launch_bounds__(NT) void qk_sweep_pass_kernel(SweepArgs a, const qk
             job = job0;
         }
         const int64_t job_c = job < njobs ? job : njobs - 1;  // padded tile slots reuse a valid row
+        int64_t srow = job_c, brow = 0;  // rows of the slot table and of the binding table
+        if (BOUND) {
+            brow = job_c / a.jobs_per_binding;
+            srow = job_c - brow * a.jobs_per_binding;
+        }
 
         for (int o = grp.op_begin; o < grp.op_end; ++o) {
             const qk_op op = g_ops[o];
@@ -355,7 +367,10 @@ __global__ __launch_bounds__(NT) void qk_sweep_pass_kernel(SweepArgs a, const qk
                     dispatch_d1(op.a, v, m);
                 } break;
                 case QK_SLOT:
-                    dispatch_u1(op.a, v, a.job_slots + (job_c * a.n_slots + op.slot) * 8);
+                    dispatch_u1(op.a, v, a.job_slots + (srow * a.n_slots + op.slot) * 8);
+                    break;
+                case QK_PARAM:
+                    if (BOUND) dispatch_u1(op.a, v, a.bind_mats + (brow * a.n_params + op.slot) * 8);
                     break;
                 case QK_U2: dispatch_u2(op.a, op.b, v, mp); break;
                 case QK_D2: dispatch_d2(op.a, op.b, v, mp); break;
@@ -423,7 +438,7 @@ __global__ __launch_bounds__(NT) void qk_sweep_pass_kernel(SweepArgs a, const qk
             job = job0;
             x = local_to_state(t) & mmask;
         }
-        if (job < njobs) a.pjob[(job << a.m) + (int64_t)x] = a.job_sign[job] * acc;
+        if (job < njobs) a.pjob[(job << a.m) + (int64_t)x] = a.job_sign[BOUND ? job % a.jobs_per_binding : job] * acc;
     }
 }
 
@@ -1649,10 +1664,19 @@ int qk_sweep_workspace_bytes(const qk_program* p, int64_t n_jobs, int64_t* bytes
     return QK_OK;
 }
 
-int qk_sweep(qk_ctx* ctx, const qk_program* p, int64_t n_jobs, const double* job_slots,
-             const double* job_sign, void* workspace, int64_t workspace_bytes, double* pjob) {
+}  // extern "C"
+
+namespace {
+
+// qk_sweep's checks and launches. bind_mats == nullptr: the unbound kernels over n_jobs jobs; else the BOUND
+// kernels over n_jobs units of jobs_per_binding jobs per binding.
+int sweep_interpreter(qk_ctx* ctx, const qk_program* p, int64_t n_jobs, const double* job_slots,
+                      const double* job_sign, void* workspace, int64_t workspace_bytes, double* pjob,
+                      bool bound, const double* bind_mats, int32_t n_params, int64_t jobs_per_binding) {
     if (!ctx) return QK_EARG;
     if (!p || !p->passes || p->n_passes < 1) return fail(ctx, QK_EARG, "qk_sweep: empty program%s");
+    if (!bound && program_has_params(p))
+        return fail(ctx, QK_EARG, "qk_sweep: the program holds run-time parameters (QK_PARAM): use qk_sweep_bound%s");
     if (n_jobs <= 0) return QK_OK;
     if (!job_sign || !pjob || (p->n_slots > 0 && !job_slots))
         return fail(ctx, QK_EARG, "qk_sweep: null buffer%s");
@@ -1683,6 +1707,9 @@ int qk_sweep(qk_ctx* ctx, const qk_program* p, int64_t n_jobs, const double* job
     a.n_eff = p->n_eff;
     a.m = p->m;
     a.n_slots = p->n_slots;
+    a.bind_mats = bind_mats;
+    a.jobs_per_binding = jobs_per_binding;
+    a.n_params = n_params;
     for (int ip = 0; ip < p->n_passes; ++ip) {
         const qk_pass& ps = p->passes[ip];
         if (!p->packed && __builtin_popcountll(ps.tile_mask) != QK_TILE_BITS)
@@ -1702,17 +1729,43 @@ int qk_sweep(qk_ctx* ctx, const qk_program* p, int64_t n_jobs, const double* job
             const int64_t per = (int64_t)1 << (QK_TILE_BITS - p->n_eff);
             const int64_t blocks = (n_jobs + per - 1) / per;
             if (blocks > 0x7fffffff) return fail(ctx, QK_EARG, "qk_sweep: too many jobs%s");
-            hipLaunchKernelGGL(qk_sweep_pass_kernel<true>, dim3((unsigned)blocks), dim3(NT), 0, ctx->stream, a,
-                               a.ops, a.groups, a.mats);
+            if (bound)
+                hipLaunchKernelGGL((qk_sweep_pass_kernel<true, true>), dim3((unsigned)blocks), dim3(NT), 0, ctx->stream,
+                                   a, a.ops, a.groups, a.mats);
+            else
+                hipLaunchKernelGGL((qk_sweep_pass_kernel<true, false>), dim3((unsigned)blocks), dim3(NT), 0, ctx->stream,
+                                   a, a.ops, a.groups, a.mats);
         } else {
             const int64_t blocks = a.init_sparse ? n_jobs : (n_jobs << (p->n - QK_TILE_BITS));
             if (blocks > 0x7fffffff) return fail(ctx, QK_EARG, "qk_sweep: too many tiles%s");
-            hipLaunchKernelGGL(qk_sweep_pass_kernel<false>, dim3((unsigned)blocks), dim3(NT), 0, ctx->stream, a,
-                               a.ops, a.groups, a.mats);
+            if (bound)
+                hipLaunchKernelGGL((qk_sweep_pass_kernel<false, true>), dim3((unsigned)blocks), dim3(NT), 0, ctx->stream,
+                                   a, a.ops, a.groups, a.mats);
+            else
+                hipLaunchKernelGGL((qk_sweep_pass_kernel<false, false>), dim3((unsigned)blocks), dim3(NT), 0, ctx->stream,
+                                   a, a.ops, a.groups, a.mats);
         }
         QK_HIP(ctx, hipGetLastError());
     }
     return QK_OK;
+}
+
+}  // namespace
+
+int sweep_interpreter_bound(qk_ctx* ctx, const qk_program* p, int64_t n_units, int64_t jobs_per_binding,
+                            int32_t n_params, const double* bind_mats, const double* job_slots,
+                            const double* job_sign, void* workspace, int64_t workspace_bytes, double* pjob) {
+    if (jobs_per_binding < 1) return fail(ctx, QK_EARG, "qk_sweep_bound: no jobs%s");
+    return sweep_interpreter(ctx, p, n_units, job_slots, job_sign, workspace, workspace_bytes, pjob, true, bind_mats,
+                             n_params, jobs_per_binding);
+}
+
+extern "C" {
+
+int qk_sweep(qk_ctx* ctx, const qk_program* p, int64_t n_jobs, const double* job_slots,
+             const double* job_sign, void* workspace, int64_t workspace_bytes, double* pjob) {
+    return sweep_interpreter(ctx, p, n_jobs, job_slots, job_sign, workspace, workspace_bytes, pjob, false, nullptr, 0,
+                             1);
 }
 
 int qk_reduce_labels(qk_ctx* ctx, int64_t n_labels, const int64_t* offsets, int64_t width,

@@ -136,6 +136,9 @@ int sweep_compiled(qk_ctx* ctx, const qk_module* module, const qk_program* p, in
     if (!module || !p || !p->passes || p->n_passes < 1) return jfail(ctx, QK_EARG, "qk_sweep_compiled: empty program");
     if ((int)module->fns.size() != p->n_passes)
         return jfail(ctx, QK_EARG, "qk_sweep_compiled: module does not hold one kernel per pass");
+    if (program_has_params(p))
+        return jfail(ctx, QK_EARG, "qk_sweep_compiled: the program holds run-time parameters (QK_PARAM): use "
+                                   "qk_sweep_bound");
     if (n_jobs <= 0) return QK_OK;
     if (p->packed || p->n <= QK_TILE_BITS || p->n > 40)
         return jfail(ctx, QK_EARG, "qk_sweep_compiled: SPLIT programs only");
@@ -217,6 +220,8 @@ int sweep_compiled_multi(qk_ctx* ctx, const qk_module* module, int n_prog, const
         const qk_program& p = progs[f];
         if (p.packed || !p.passes || p.n_passes < 1 || p.n > 40)
             return jfail(ctx, QK_EARG, "qk_sweep_compiled_multi: SPLIT programs only");
+        if (program_has_params(&p))
+            return jfail(ctx, QK_EARG, "qk_sweep_compiled_multi: a program holds run-time parameters (QK_PARAM)");
         const int t = __builtin_popcountll(p.passes[0].tile_mask);
         if ((f && t != tb) || t < QK_JIT_TILE_MIN || t > QK_JIT_TILE_MAX || t >= p.n)
             return jfail(ctx, QK_EARG, "qk_sweep_compiled_multi: programs need one tile width of 10 to 13 bits");
@@ -318,6 +323,109 @@ int qk_sweep_compiled_labels(qk_ctx* ctx, const qk_module* module, const qk_prog
         return jfail(ctx, QK_EARG, "qk_sweep_compiled_labels: too many tiles");
     return sweep_compiled(ctx, module, p, n_jobs, job_slots, job_sign, workspace, workspace_bytes, q, n_labels,
                           label_offsets);
+}
+
+}  // extern "C"
+
+// ---- bound sweep: run-time parameter tables --------------------------------------------------------
+namespace {
+
+// The checks of qk_sweep_bound that need no device; msg: what was refused.
+int bound_check(const qk_program* p, const qk_op* ops_host, int64_t n_ops, int64_t n_bind, int32_t n_params,
+                const double* bind_mats, int64_t n_jobs, int64_t workspace_bytes, const char** msg) {
+    *msg = "";
+    if (!p || !p->passes || p->n_passes < 1) return *msg = "empty program", QK_EARG;
+    if (n_bind < 1) return *msg = "n_bind < 1", QK_EARG;
+    if (n_jobs < 1) return *msg = "n_jobs < 1", QK_EARG;
+    if (n_params < 0) return *msg = "n_params < 0", QK_EARG;
+    if (n_params > 0 && !bind_mats) return *msg = "null bind_mats with n_params > 0", QK_EARG;
+    if (n_ops < 0 || (n_ops > 0 && !ops_host)) return *msg = "null ops_host", QK_EARG;
+    if (p->n < 1 || p->n > 40 || p->n_eff < p->n || p->n_eff > 40) return *msg = "bad widths", QK_EARG;
+    if (n_bind > (INT64_MAX >> (p->n_eff + 5)) / n_jobs) return *msg = "too many units", QK_EARG;
+    int64_t need = 0;
+    if (qk_sweep_bound_workspace_bytes(p, n_bind, n_jobs, &need) != QK_OK) return *msg = "bad sizes", QK_EARG;
+    if (workspace_bytes < need) return *msg = "workspace below n_bind * n_jobs states", QK_EARG;
+    // every op belongs to exactly one pass (groups and their ops are consecutive): a QK_PARAM op needs an index
+    // below n_params and at least one pass that declares QK_PASS_PARAM
+    bool any_param = false;
+    for (int64_t o = 0; o < n_ops; ++o) {
+        if (ops_host[o].kind != QK_PARAM) continue;
+        any_param = true;
+        if (ops_host[o].slot < 0 || ops_host[o].slot >= n_params) return *msg = "param index >= n_params", QK_EARG;
+        if (ops_host[o].a < 0 || ops_host[o].a >= QK_FIBER_BITS) return *msg = "param op off the fiber", QK_EARG;
+    }
+    if (any_param != program_has_params(p)) return *msg = "QK_PASS_PARAM flags do not match the ops", QK_EARG;
+    return QK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qk_sweep_bound_workspace_bytes(const qk_program* p, int64_t n_bind, int64_t n_jobs, int64_t* bytes) {
+    if (!p || !bytes || n_bind < 0 || n_jobs < 0) return QK_EARG;
+    return qk_sweep_workspace_bytes(p, n_bind * n_jobs, bytes);
+}
+
+int qk_sweep_bound_check(const qk_program* p, const qk_op* ops_host, int64_t n_ops, int64_t n_bind, int32_t n_params,
+                         const double* bind_mats, int64_t n_jobs, int64_t workspace_bytes) {
+    const char* msg;
+    return bound_check(p, ops_host, n_ops, n_bind, n_params, bind_mats, n_jobs, workspace_bytes, &msg);
+}
+
+int qk_sweep_bound(qk_ctx* ctx, const qk_module* module, const qk_program* p, const qk_op* ops_host, int64_t n_ops,
+                   int64_t n_bind, int32_t n_params, const double* bind_mats, int64_t n_jobs,
+                   const double* job_slots, const double* job_sign, int64_t n_labels, const int64_t* label_off,
+                   void* workspace, int64_t workspace_bytes, double* out) {
+    if (!ctx) return QK_EARG;
+    const char* msg;
+    if (bound_check(p, ops_host, n_ops, n_bind, n_params, bind_mats, n_jobs, workspace_bytes, &msg) != QK_OK)
+        return jfail(ctx, QK_EARG, std::string("qk_sweep_bound: ") + msg);
+    if (!job_sign || !out || (p->n_slots > 0 && !job_slots)) return jfail(ctx, QK_EARG, "qk_sweep_bound: null buffer");
+    const int64_t n_units = n_bind * n_jobs;
+    if (!module) {
+        if (label_off) return jfail(ctx, QK_EARG, "qk_sweep_bound: label offsets need a module (per-program kernels)");
+        return sweep_interpreter_bound(ctx, p, n_units, n_jobs, n_params, bind_mats, job_slots, job_sign, workspace,
+                                       workspace_bytes, out);
+    }
+    if (!program_has_params(p))
+        return jfail(ctx, QK_EARG, "qk_sweep_bound: a module's kernels take the binding table only for a program "
+                                   "with QK_PARAM ops (use qk_sweep_compiled)");
+    if ((int)module->fns.size() != p->n_passes)
+        return jfail(ctx, QK_EARG, "qk_sweep_bound: module does not hold one kernel per pass");
+    if (p->packed || p->n <= QK_TILE_BITS) return jfail(ctx, QK_EARG, "qk_sweep_bound: a module runs SPLIT programs only");
+    if (label_off && n_labels < 1) return jfail(ctx, QK_EARG, "qk_sweep_bound: label offsets need n_labels >= 1");
+    if (!workspace) return jfail(ctx, QK_EARG, "qk_sweep_bound: null workspace");
+    if (hipSetDevice(ctx->device) != hipSuccess) return jfail(ctx, QK_EHIP, "qk_sweep_bound: hipSetDevice");
+    const int64_t rows = label_off ? n_labels : n_jobs;  // FINAL output rows per binding
+    for (int ip = 0; ip < p->n_passes; ++ip) {
+        const bool sparse_init = ip == 0 && p->n_passes > 1;
+        const bool fin = ip == p->n_passes - 1;
+        const int tb = __builtin_popcountll(p->passes[ip].tile_mask);
+        if (tb < QK_JIT_TILE_MIN || tb > QK_JIT_TILE_MAX || tb >= p->n)
+            return jfail(ctx, QK_EARG, "qk_sweep_bound: tiles must hold 10 to 13 state bits");
+        const int64_t groups = fin ? n_bind * rows : n_units;
+        const int64_t blocks = sparse_init ? n_units : (groups << (p->n - tb));
+        if (blocks > 0x7fffffff) return jfail(ctx, QK_EARG, "qk_sweep_bound: too many tiles");
+        // the bound form's kernel arguments (sweep_codegen._pass_kernel): n_jobs is the FINAL rows per binding
+        struct {
+            const double* slots;
+            const double* sign;
+            void* state;
+            double* pjob;
+            int64_t n_jobs;
+            const int64_t* label_off;
+            const double* bind_mats;
+            int64_t jobs_per_binding;
+        } args{job_slots, job_sign, workspace, out, rows, fin ? label_off : nullptr, bind_mats, n_jobs};
+        size_t size = sizeof(args);
+        void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                       HIP_LAUNCH_PARAM_END};
+        const hipError_t e = hipModuleLaunchKernel(module->fns[ip], (unsigned)blocks, 1, 1, 1u << (tb - 4), 1, 1, 0,
+                                                   ctx->stream, nullptr, cfg);
+        if (e != hipSuccess) return jfail(ctx, QK_EHIP, std::string("qk_sweep_bound: ") + hipGetErrorString(e));
+    }
+    return QK_OK;
 }
 
 }  // extern "C"

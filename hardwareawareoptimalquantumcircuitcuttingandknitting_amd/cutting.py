@@ -23,7 +23,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
-from .circuit import CircuitInstruction, Gate, QuantumCircuit, QuantumRegister
+from .circuit import CircuitInstruction, Gate, QuantumCircuit, QuantumRegister, is_parametric
 from .generators import factor_int, gen_circ
 from .virtual_gates import VIRTUAL_GATE_TYPES, VirtualMove
 
@@ -37,13 +37,14 @@ def _decompose_2q(circ: QuantumCircuit) -> QuantumCircuit:
         if name == "cz":
             out.h(qs[1]); out.cx(qs[0], qs[1]); out.h(qs[1])
         elif name == "cp":
-            lam = float(op.params[0])
+            lam = op.params[0] if is_parametric(op) else float(op.params[0])
             out.p(lam / 2, qs[0]); out.cx(qs[0], qs[1]); out.p(-lam / 2, qs[1])
             out.cx(qs[0], qs[1]); out.p(lam / 2, qs[1])
         elif name == "cy":
             out.sdg(qs[1]); out.cx(qs[0], qs[1]); out.s(qs[1])
         elif name == "rzz":
-            out.cx(qs[0], qs[1]); out.rz(float(op.params[0]), qs[1]); out.cx(qs[0], qs[1])
+            out.cx(qs[0], qs[1]); out.rz(op.params[0] if is_parametric(op) else float(op.params[0]), qs[1])
+            out.cx(qs[0], qs[1])
         elif name == "swap":
             out.cx(qs[0], qs[1]); out.cx(qs[1], qs[0]); out.cx(qs[0], qs[1])
         else:
@@ -119,6 +120,10 @@ def cut_circuit(circ: QuantumCircuit, spec: CutSpec) -> QuantumCircuit:
         if idx in gate_cuts:
             if len(qs) != 2 or op.name not in VIRTUAL_GATE_TYPES:
                 raise ValueError(f"instruction {idx} ({op.name}) cannot be gate-cut")
+            if is_parametric(op):
+                # the knit coefficients of a virtual gate are part of the plan: its parameters are constants
+                raise ValueError(f"instruction {idx} ({op!r}) holds a parameter expression: a cut gate must have "
+                                 "constant parameters (bind the circuit first, or cut another gate)")
             # label as the cutter names it (Cutter.py:585-589); params copied, not aliased
             vg = VIRTUAL_GATE_TYPES[op.name](Gate(op.name, 2, list(op.params)), f"{op.name} {idx}")
             out.append(vg, qs)

@@ -34,7 +34,7 @@ from . import _lib
 from .fragment_program import (FragmentProgram, JobTable, basis_reduce, build_jobs, compile_fragment,
                                dedup_labels)
 from .knit_plan import LabelSpace, deposit_keys, factor_vgate
-from .sweep_plan import K_SLOT, EncodedProgram, encode
+from .sweep_plan import K_SLOT, LOW_BITS, EncodedProgram, encode
 
 _torch = None
 
@@ -1409,6 +1409,9 @@ class FragmentState:
     fold: int = 1
     # per-program kernels: (compiled, tile bits, FINAL tile bits) as prepare_fragments chose them
     jit: tuple = (False, None, None)
+    # bound sweeps (sweep_fragment_bound): the job tables on the device, uploaded on first use and kept
+    # (they do not depend on the binding)
+    device_jobs: tuple | None = None
 
     @property
     def swept_labels(self) -> list:
@@ -1493,7 +1496,14 @@ def host_planning():
 
 
 def prepare_fragments(virt, device: int = 0, upload: bool = True, dedup: bool = True,
-                      basis: bool = False, jit: bool | None = None, relevance: bool = True) -> list[FragmentState]:
+                      basis: bool = False, jit: bool | None = None, relevance: bool = True,
+                      parametric: bool = False) -> list[FragmentState]:
+    """``parametric``: the caller sweeps with a binding table (``sweep_fragment_bound``). Every other
+    route evaluates a program whose matrices are all constants, so a circuit that still holds
+    parameters is refused here."""
+    if not parametric and getattr(virt, "parameters", None):
+        raise ValueError(f"the circuit holds {len(virt.parameters)} unbound parameters: bind it "
+                         "(QuantumCircuit.bind) or sweep it with parametric.ParametricKnit")
     with host_planning():
         return _prepare_fragments(virt, device, upload, dedup, basis, jit, relevance)
 
@@ -1514,7 +1524,7 @@ def _prepare_fragments(virt, device: int, upload: bool, dedup: bool, basis: bool
     for frag, fcirc in virt.fragment_circuits.items():
         if len(frag) == 0:
             continue
-        prog = compile_fragment(fcirc, frag, cl)
+        prog = compile_fragment(fcirc, frag, cl, parameters=getattr(virt, "parameters", None) or None)
         labels = virt.get_instance_labels(frag)
         touches = [bool(set(v.qubits) & set(frag)) for v in vg]
         if dedup:
@@ -1533,6 +1543,9 @@ def _prepare_fragments(virt, device: int, upload: bool, dedup: bool, basis: bool
     split = [(fs.prog.n, fs.jobs.n_jobs) for fs, w in zip(out, want) if w and not fs.dropped and fs.prog.n > 12]
     tb = jit_tile_bits(split) if split else JIT_TILE_BITS_MAX
     jit_progs = [_device_program(fs.prog)[0] for fs, w in zip(out, want) if w and not fs.dropped and fs.prog.n > 12]
+    # a FINAL tile holds the low bits and every traced qubit (sweep_plan.schedule_passes): a narrower width,
+    # chosen for a small batch or forced, is raised to the narrowest that can
+    tb = min(max([tb] + [LOW_BITS + p.n - p.m for p in jit_progs]), JIT_TILE_BITS_MAX)
     ftb = jit_final_tile_bits(jit_progs, tb) if jit_progs else None
     for fs, w in zip(out, want):
         fs.jit = (bool(w and _jit_enabled()), tb, ftb)  # what upload compiles (jit_sources)
@@ -1569,7 +1582,7 @@ def jit_sources(virt, basis: bool = False, relevance: bool = True) -> list:
         encs.append(encode(dprog, tile_bits=tb or JIT_TILE_BITS_MAX, final_tile_bits=ftb))
     out = [sweep_codegen.generate(e) for e in encs]
     rounds = max((len(e.passes) for e in encs), default=0)
-    if 2 <= len(encs) <= 4 and all(len({e.pass_tile_bits(r) for e in encs if len(e.passes) > r}) == 1
+    if 2 <= len(encs) <= 4 and not any(e.n_params for e in encs) and all(len({e.pass_tile_bits(r) for e in encs if len(e.passes) > r}) == 1
                                    for r in range(rounds)):
         out.append(sweep_codegen.generate_multi(encs))
     return out
@@ -1592,6 +1605,9 @@ def sweep_fragment(ctx: Context, fs: FragmentState, label_range=None):
     swept (deduplicated) instances: ``q[fs.row_of_label()]`` is per label.
     """
     T = torch()
+    if fs.prog.params:
+        raise ValueError("the fragment holds run-time parameters: sweep it with sweep_fragment_bound "
+                         "(parametric.ParametricKnit)")
     jobs = fs.jobs
     lo, hi = (0, fs.n_rows) if label_range is None else label_range
     width = 1 << fs.prog.m
@@ -1607,6 +1623,84 @@ def sweep_fragment(ctx: Context, fs: FragmentState, label_range=None):
     if sub.n_jobs == hi - lo:  # no branching: jobs are labels
         return fold_traced(ctx, pjob, fs.fold)
     return fold_traced(ctx, reduce_labels(ctx, pjob, off_t, hi - lo), fs.fold)
+
+
+BOUND_WORKSPACE_BYTES = 1 << 30  # state workspace of one bound sweep launch: more bindings go in chunks
+
+
+def binding_chunks(n_bind: int, unit_bytes: int, budget: int) -> list:
+    """``[(b0, b1), ...]``: consecutive runs of bindings whose ``unit_bytes`` each stay within ``budget``
+    together (at least one binding per chunk)."""
+    per = max(1, int(budget) // max(int(unit_bytes), 1))
+    return [(b, min(b + per, n_bind)) for b in range(0, n_bind, per)]
+
+
+_BOUND_OFFS: dict = {}
+
+
+def _bound_label_offsets(off_t, n_bind: int, n_jobs: int):
+    """Label offsets of ``n_bind`` bindings' per-unit rows (binding b's jobs start at ``b * n_jobs``)."""
+    T = torch()
+    key = (off_t.data_ptr(), n_bind, n_jobs)
+    got = _BOUND_OFFS.get(key)
+    if got is None:
+        if len(_BOUND_OFFS) > 64:
+            _BOUND_OFFS.clear()
+        shift = T.arange(n_bind, dtype=T.int64, device=off_t.device)[:, None] * n_jobs
+        offs = T.cat([(off_t[:-1][None, :] + shift).reshape(-1), off_t.new_tensor([n_bind * n_jobs])])
+        got = _BOUND_OFFS[key] = (offs, off_t)  # keeps off_t alive: its address is the key
+    return got[0]
+
+
+def sweep_fragment_bound(ctx: Context, fs: FragmentState, mats, workspace_budget: int | None = None):
+    """Signed-folded distributions of one fragment for ``B`` parameter bindings at once: ``mats``
+    complex ``[B, n_params, 2, 2]`` (``FragmentProgram.bind_matrices``) -> device fp64
+    ``[B, rows, 2^m]``, rows as :func:`sweep_fragment`. One ``qk_sweep_bound`` launch sequence per
+    chunk of bindings (:func:`binding_chunks`: the state workspace stays under ``workspace_budget``,
+    default ``BOUND_WORKSPACE_BYTES``); nothing is compiled and the program is the same for every
+    binding. A unit's arithmetic does not depend on the units swept with it, so a row has the same
+    bits whatever the batch or the chunking."""
+    T = torch()
+    dev = T.device("cuda", ctx.device)
+    mats = np.ascontiguousarray(np.asarray(mats, dtype=np.complex128))
+    P = fs.prog.num_params
+    if mats.ndim != 4 or mats.shape[1:] != (P, 2, 2) or mats.shape[0] < 1:
+        raise ValueError(f"binding matrices must be [B >= 1, {P}, 2, 2], not {mats.shape}")
+    B, rows = mats.shape[0], fs.n_rows
+    if fs.dropped:
+        return T.ones((B, rows, 1), dtype=T.float64, device=dev)
+    if P == 0:  # nothing to bind in this fragment: one sweep serves every binding
+        return sweep_fragment(ctx, fs).unsqueeze(0).expand(B, -1, -1).contiguous()
+    dprog, jobs = fs.dprog, fs.jobs
+    enc = dprog.enc
+    if fs.device_jobs is None:
+        fs.device_jobs = jobs_to_device(jobs, ctx.device)
+    slot_t, sign_t, off_t = fs.device_jobs
+    n_jobs, width = jobs.n_jobs, 1 << enc.m
+    branching = n_jobs != rows
+    labels = branching and dprog.module is not None  # fused FINAL: rows are labels straight from the sweep
+    bind_t = T.from_numpy(mats.view(np.float64).reshape(B, P * 8)).to(dev)
+    out = T.empty((B, rows, width), dtype=T.float64, device=dev)
+    budget = BOUND_WORKSPACE_BYTES if workspace_budget is None else int(workspace_budget)
+    chunks = binding_chunks(B, n_jobs * (16 << enc.n_eff), budget)
+    need = ctypes.c_int64()
+    ctx.check(ctx.lib.qk_sweep_bound_workspace_bytes(ctypes.byref(dprog.struct), chunks[0][1] - chunks[0][0], n_jobs,
+                                                     ctypes.byref(need)), "qk_sweep_bound_workspace_bytes")
+    workspace = T.empty(max(need.value, 1), dtype=T.uint8, device=dev)
+    ops_host = enc.ops.ctypes.data if len(enc.ops) else None
+    for b0, b1 in chunks:
+        nb = b1 - b0
+        pjob = out[b0:b1] if (labels or not branching) else T.empty((nb * n_jobs, width), dtype=T.float64, device=dev)
+        ctx.check(ctx.lib.qk_sweep_bound(ctx.handle, dprog.module, ctypes.byref(dprog.struct), ops_host, len(enc.ops),
+                                         nb, P, bind_t.data_ptr() + b0 * P * 64, n_jobs, slot_t.data_ptr(),
+                                         sign_t.data_ptr(), rows if labels else 0, off_t.data_ptr() if labels else None,
+                                         workspace.data_ptr(), need.value, pjob.data_ptr()), "qk_sweep_bound")
+        if branching and not labels:
+            reduce_labels(ctx, pjob, _bound_label_offsets(off_t, nb, n_jobs), nb * rows,
+                          q=out[b0:b1].view(nb * rows, width))
+    if fs.fold > 1:
+        out = fold_traced(ctx, out.view(B * rows, width), fs.fold).view(B, rows, width // fs.fold)
+    return out
 
 
 @dataclass

@@ -29,7 +29,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import gates as _g
-from .circuit import CompositeInstruction
+from .circuit import CompositeInstruction, ParameterExpression, is_parametric
 from .virtual_gates import VirtualGateEndpoint, _memoised, planning_memo  # noqa: F401 (planning_memo re-exported)
 
 P0 = np.array([[1, 0], [0, 0]], dtype=np.complex128)
@@ -43,10 +43,13 @@ class UnsupportedCircuit(ValueError):
 
 @dataclass
 class HostOp:
-    kind: str  # "u1" | "u2" | "slot"
+    kind: str  # "u1" | "u2" | "slot" | "param"
     qubits: tuple
     mat: np.ndarray | None = None
-    slot: int = -1
+    slot: int = -1  # "slot": index into prog.slots; "param": index into prog.params
+    # "param": the run's factors in application order, each a constant 2x2 matrix or a
+    # (gate name, [angle: float or ParameterExpression]) pair; its matrix exists per binding only
+    factors: list | None = None
 
 
 @dataclass
@@ -67,10 +70,39 @@ class FragmentProgram:
     ops: list
     slots: list
     qubit_order: list  # fragment Qubit objects in local order
+    params: list = field(default_factory=list)  # the "param" ops, in program order (HostOp.slot indexes it)
+    parameters: list = field(default_factory=list)  # the Parameters a row of binding values is ordered by
 
     @property
     def num_slots(self) -> int:
         return len(self.slots)
+
+    @property
+    def num_params(self) -> int:
+        return len(self.params)
+
+    def bind_matrices(self, values) -> np.ndarray:
+        """complex128 ``[B, num_params, 2, 2]``: the matrix of every param op for each row of
+        ``values [B, P]`` (columns in :attr:`parameters` order), the product of its factors evaluated
+        on the host, vectorised over ``B``."""
+        values = np.asarray(values, dtype=np.float64)
+        if values.ndim != 2 or values.shape[1] != len(self.parameters):
+            raise ValueError(f"binding values must be [B, {len(self.parameters)}], not {values.shape}")
+        B = values.shape[0]
+        column = {p: i for i, p in enumerate(self.parameters)}
+        out = np.empty((B, len(self.params), 2, 2), dtype=np.complex128)
+        for k, op in enumerate(self.params):
+            acc = None
+            for f in op.factors:
+                if isinstance(f, np.ndarray):
+                    m = np.broadcast_to(f, (B, 2, 2))
+                else:
+                    name, angles = f
+                    m = _g.gate_matrix_batch(name, [a.evaluate_batch(values, column) if isinstance(a, ParameterExpression)
+                                                    else np.full(B, float(a)) for a in angles])
+                acc = m if acc is None else np.matmul(m, acc)
+            out[:, k] = acc
+        return out
 
 
 def _op_matrix(op) -> np.ndarray:
@@ -97,11 +129,36 @@ def _flatten(instructions, qmap_fn):
             yield op, tuple(qmap_fn(q) for q in instr.qubits), tuple(instr.clbits)
 
 
-def compile_fragment(frag_circuit, fragment, clbit_index) -> FragmentProgram:
+_CX = _g.gate_matrix("cx")
+
+
+def _lower_parametric_2q(name: str, qs: tuple, params: list) -> list:
+    """A parametric ``rzz`` / ``cp`` / ``cu1`` on an uncut pair as ``cx`` and one-qubit parametric gates (raw ops
+    in application order): ``rzz(t) = cx . rz(t)_target . cx`` and ``cp(l) = p(l/2)_a . cx . p(-l/2)_b . cx .
+    p(l/2)_b``, both exact. Any other gate of two or more qubits that holds an expression is refused."""
+    a, b = qs
+    cx = lambda: ("u2", (a, b), _CX.copy())  # noqa: E731
+    if name == "rzz":
+        return [cx(), ("p1", (b,), ("rz", [params[0]])), cx()]
+    if name in ("cp", "cu1"):
+        lam = params[0]
+        return [("p1", (a,), ("p", [lam / 2])), cx(), ("p1", (b,), ("p", [-lam / 2])), cx(),
+                ("p1", (b,), ("p", [lam / 2]))]
+    raise UnsupportedCircuit(f"gate '{name}' on {len(qs)} qubits holds a parameter expression: only rzz, cp and "
+                             "cu1 are lowered to run-time one-qubit gates")
+
+
+def compile_fragment(frag_circuit, fragment, clbit_index, parameters=None) -> FragmentProgram:
     """Compile one fragment circuit (endpoints still in place).
 
     ``clbit_index(clbit) -> int`` maps a classical bit to its global index in
-    the ``meas``-first clbit order of the cut circuit.
+    the ``meas``-first clbit order of the cut circuit. ``parameters``: the order of a row of binding
+    values (the whole circuit's ``parameters``); None: the fragment's own, in order of first appearance.
+
+    A one-qubit gate that holds a parameter expression stays symbolic: the maximal run of one-qubit
+    gates around it becomes one ``"param"`` op whose matrix is read per binding at run time. Nothing
+    the plan decides may depend on its values, so a param op is never elided as an identity, never
+    matched by :func:`_recover_cz` and never absorbed into a cut slot.
     """
     frag_qubits = list(fragment)
     n = len(frag_qubits)
@@ -128,6 +185,14 @@ def compile_fragment(frag_circuit, fragment, clbit_index) -> FragmentProgram:
             nq = len(qs)
             if nq not in (1, 2):
                 raise UnsupportedCircuit(f"{nq}-qubit gate '{name}' is not supported (decompose first)")
+            if is_parametric(op):
+                if nq == 1:
+                    if name not in _g.ONE_QUBIT_BATCH:
+                        raise UnsupportedCircuit(f"gate '{name}' cannot hold a parameter expression")
+                    raw.append(("p1", qs, (name, list(op.params))))
+                else:
+                    raw.extend(_lower_parametric_2q(name, qs, list(op.params)))
+                continue
             raw.append(("u1" if nq == 1 else "u2", qs, _op_matrix(op)))
     for q, (pos, _) in measured_at.items():
         for kind, qs, _ in raw[pos + 1 :]:
@@ -149,12 +214,22 @@ def compile_fragment(frag_circuit, fragment, clbit_index) -> FragmentProgram:
     # -- pass 2: fuse 1-qubit runs, build slots
     ops: list[HostOp] = []
     slots: list[SlotSpec] = []
-    pending: dict[int, np.ndarray] = {}
+    params: list[HostOp] = []
+    # per qubit the open run of one-qubit gates: constant matrices (adjacent ones multiplied) and
+    # symbolic (name, angles) factors, in application order
+    pending: dict[int, list] = {}
 
     def flush(q):
-        mat = pending.pop(q, None)
-        if mat is not None and not _g.is_identity_up_to_phase(mat):
-            ops.append(HostOp("u1", (q,), mat))
+        run = pending.pop(q, None)
+        if run is None:
+            return
+        if len(run) == 1 and isinstance(run[0], np.ndarray):
+            if not _g.is_identity_up_to_phase(run[0]):
+                ops.append(HostOp("u1", (q,), run[0]))
+            return
+        op = HostOp("param", (q,), None, len(params), run)
+        params.append(op)
+        ops.append(op)
 
     for kind, qs, payload in raw:
         lq = tuple(loc[q] for q in qs)
@@ -162,7 +237,13 @@ def compile_fragment(frag_circuit, fragment, clbit_index) -> FragmentProgram:
             continue
         if kind == "u1":
             q = lq[0]
-            pending[q] = payload @ pending.get(q, I2)
+            run = pending.setdefault(q, [])
+            if run and isinstance(run[-1], np.ndarray):
+                run[-1] = payload @ run[-1]
+            else:
+                run.append(payload @ I2)
+        elif kind == "p1":
+            pending.setdefault(lq[0], []).append(payload)
         elif kind == "u2":
             for q in lq:
                 flush(q)
@@ -178,8 +259,11 @@ def compile_fragment(frag_circuit, fragment, clbit_index) -> FragmentProgram:
 
     # -- pass 3: absorb fixed 1q gates adjacent (per qubit) to a slot into it
     _absorb_into_slots(ops, slots)
+    if parameters is None:
+        parameters = list(dict.fromkeys(p for op in params for f in op.factors if not isinstance(f, np.ndarray)
+                                        for a in f[1] if isinstance(a, ParameterExpression) for p in a.terms))
     return FragmentProgram(n=n, m=m, clbits=clbits, ops=ops, slots=slots,
-                           qubit_order=[frag_qubits[q] for q in order])
+                           qubit_order=[frag_qubits[q] for q in order], params=params, parameters=list(parameters))
 
 
 _H = _g.gate_matrix("h")

@@ -116,14 +116,93 @@ TWO_QUBIT = {
 NON_UNITARY_NOOPS = {"barrier", "delay"}
 
 
+def _angle(p) -> float:
+    names = getattr(p, "parameter_names", None)
+    if names is not None:  # a circuit.ParameterExpression: no matrix before it is bound
+        raise ValueError(f"gate holds unbound parameter(s) {', '.join(names) or '(constant expression)'}: bind it first")
+    return float(p)
+
+
 def gate_matrix(name: str, params=()) -> np.ndarray:
-    """Matrix of a named gate; raises ``ValueError`` for unknown names."""
-    params = [float(p) for p in params]
+    """Matrix of a named gate; raises ``ValueError`` for unknown names and for a gate that still
+    holds a parameter expression (naming the parameter)."""
+    params = [_angle(p) for p in params]
     if name in ONE_QUBIT:
         return ONE_QUBIT[name](*params)
     if name in TWO_QUBIT:
         return TWO_QUBIT[name](*params)
     raise ValueError(f"unsupported gate '{name}'")
+
+
+def _u3_batch(theta, phi, lam) -> np.ndarray:
+    c, s = np.cos(theta / 2.0), np.sin(theta / 2.0)
+    out = np.empty(theta.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = c
+    out[..., 0, 1] = -np.exp(1j * lam) * s
+    out[..., 1, 0] = np.exp(1j * phi) * s
+    out[..., 1, 1] = np.exp(1j * (phi + lam)) * c
+    return out
+
+
+def _r_batch(theta, phi) -> np.ndarray:
+    c, s = np.cos(theta / 2.0), np.sin(theta / 2.0)
+    out = np.empty(theta.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = out[..., 1, 1] = c
+    out[..., 0, 1] = -1j * np.exp(-1j * phi) * s
+    out[..., 1, 0] = -1j * np.exp(1j * phi) * s
+    return out
+
+
+def _rx_batch(t) -> np.ndarray:
+    c, s = np.cos(t / 2.0), np.sin(t / 2.0)
+    out = np.empty(t.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = out[..., 1, 1] = c
+    out[..., 0, 1] = out[..., 1, 0] = -1j * s
+    return out
+
+
+def _ry_batch(t) -> np.ndarray:
+    c, s = np.cos(t / 2.0), np.sin(t / 2.0)
+    out = np.empty(t.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = out[..., 1, 1] = c
+    out[..., 0, 1] = -s
+    out[..., 1, 0] = s
+    return out
+
+
+def _rz_batch(t) -> np.ndarray:
+    out = np.zeros(t.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = np.exp(-0.5j * t)
+    out[..., 1, 1] = np.exp(0.5j * t)
+    return out
+
+
+def _p_batch(lam) -> np.ndarray:
+    out = np.zeros(lam.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = 1.0
+    out[..., 1, 1] = np.exp(1j * lam)
+    return out
+
+
+#: the one-qubit gates that take angles, vectorised over a batch of angle sets (same formulas as ONE_QUBIT)
+ONE_QUBIT_BATCH = {
+    "rx": _rx_batch,
+    "ry": _ry_batch,
+    "rz": _rz_batch,
+    "p": _p_batch,
+    "u1": _p_batch,
+    "u2": lambda phi, lam: _u3_batch(np.full_like(phi, math.pi / 2), phi, lam),
+    "u3": _u3_batch,
+    "u": _u3_batch,
+    "r": _r_batch,
+}
+
+
+def gate_matrix_batch(name: str, params) -> np.ndarray:
+    """``[B, 2, 2]`` matrices of a one-qubit rotation gate for ``params`` = one float64 ``[B]`` array per angle."""
+    if name not in ONE_QUBIT_BATCH:
+        raise ValueError(f"gate '{name}' takes no run-time parameters")
+    return ONE_QUBIT_BATCH[name](*[np.asarray(p, dtype=np.float64) for p in params])
 
 
 def num_gate_qubits(name: str) -> int:

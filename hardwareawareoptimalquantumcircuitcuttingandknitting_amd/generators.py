@@ -87,12 +87,19 @@ def sycamore(num_qubits: int, depth: int, seed: int | None = DEFAULT_SEED) -> Qu
     return qc
 
 
-def hwea(num_qubits: int, depth: int) -> QuantumCircuit:
+def hwea(num_qubits: int, depth: int, theta=None) -> QuantumCircuit:
+    """The reference's hardware-efficient ansatz at its fixed angles; ``theta``: the ``2 n (1 + depth)`` angles
+    instead, floats or ``circuit.Parameter`` s (a variational run binds them per step)."""
     n = num_qubits
-    theta = [0.0] * (2 * n * (1 + depth))
-    theta[0] = math.pi / 2
-    for i in range(2 * n, 2 * n + n // 2):
-        theta[i] = math.pi
+    if theta is not None:
+        theta = list(theta)
+        if len(theta) != 2 * n * (1 + depth):
+            raise ValueError(f"hwea({n}, {depth}) takes {2 * n * (1 + depth)} angles, not {len(theta)}")
+    else:
+        theta = [0.0] * (2 * n * (1 + depth))
+        theta[0] = math.pi / 2
+        for i in range(2 * n, 2 * n + n // 2):
+            theta[i] = math.pi
     qr = QuantumRegister(n, "q")
     qc = QuantumCircuit(qr)
     p = 0

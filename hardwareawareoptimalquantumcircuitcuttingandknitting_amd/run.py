@@ -566,7 +566,7 @@ def run_virtual_circuit_marginal(virt: VirtualCircuit, clbits, *, device: int = 
 def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device: int = 0,
                                     factored: bool | None = None, group=None, sample: bool = False,
                                     weights=None, method: str = "reduce", readout=None, mitigate: bool = False,
-                                    npd: bool = False, accuracy: float = 0.0):
+                                    npd: bool = False, accuracy: float = 0.0, bindings=None):
     """Expectation values of Pauli-Z strings on the exact knit (the quasi-distribution itself, no
     projection): ``sum_key (-1)^popcount(key & mask) R[key]`` per observable, without the 2^N output.
     ``observables``: int masks over the clbits, or ``'ZIIZ'`` strings (rightmost character = clbit 0,
@@ -583,7 +583,18 @@ def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device
     ``npd=True``: of the nearest probability distribution of the knit instead (``KnitReducer.project`` over all clbits
     with the truncation ``accuracy``, then ``projected_expectation``: passes over all outcomes, eight masks each);
     the values then lie in [-mass, mass]. ``weights`` gives the weighted sum, formed on the host; ``method`` must be
-    left at its default."""
+    left at its default.
+
+    ``bindings`` (float ``[B, P]``, columns in ``virt.parameters`` order, or a sequence of ``Parameter -> float``
+    mappings): the circuit may hold run-time parameters, and the result gains a leading binding axis (``[B, M]``, or
+    ``[B]`` with ``weights``). The batch is swept once by the :class:`parametric.ParametricKnit` of the circuit's
+    structure (``parametric.cached_knit``: built on the first call, so from the second call on ``run_time`` is the
+    bound sweep alone, without a compile). Exact knit by the ``"reduce"`` route only: no ``readout``, ``npd`` or other
+    ``method``."""
+    if bindings is not None:
+        return _bound_expectation(virt, observables, bindings, device, factored, weights,
+                                  plain=group is None and not sample and readout is None and not mitigate
+                                  and not npd and method == "reduce")
     if npd and method != "reduce":
         raise ValueError(f"npd=True has one route: method must be left at its default, not {method!r}")
     if method not in ("reduce", "spectrum", "fused"):
@@ -604,6 +615,25 @@ def run_virtual_circuit_expectation(virt: VirtualCircuit, observables, *, device
     info = RunTimeInfo(run_time, perf_counter() - now)
     log.info("Knitted in %.2fs.", info.knit_time)
     return vals, info
+
+
+def _bound_expectation(virt: VirtualCircuit, observables, bindings, device: int, factored, weights, plain: bool):
+    from . import parametric
+
+    if not plain:
+        raise ValueError("bindings: one GPU, the exact knit and method='reduce' only (no group, sample, readout, "
+                         "mitigate or npd)")
+    vals = parametric.binding_values(virt.parameters, bindings, batch=True)
+    now = perf_counter()
+    knit = parametric.cached_knit(virt, device, factored)
+    qs = knit.sweep(vals) if len(vals) else []
+    _sync(device)
+    run_time = perf_counter() - now
+    now = perf_counter()
+    out = knit.expectation_of_rows(qs, len(vals), observables, weights)
+    info = RunTimeInfo(run_time, perf_counter() - now)
+    log.info("Knitted in %.2fs.", info.knit_time)
+    return out, info
 
 
 def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed: int = 0, clbits=None,

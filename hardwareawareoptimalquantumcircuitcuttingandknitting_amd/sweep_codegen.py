@@ -170,7 +170,12 @@ def program_scale(enc) -> float:
     return out
 
 
-def _emit_op(e: _Emitter, op, mats, ext, n_slots: int) -> None:
+def has_params(enc) -> bool:
+    """Whether the program holds a K_PARAM op: its kernels then take the binding table (bound form)."""
+    return bool((enc.ops["kind"] == sp.K_PARAM).any())
+
+
+def _emit_op(e: _Emitter, op, mats, ext, n_slots: int, n_params: int = 0) -> None:
     kind, a, b, e1, e2, slot, mat = (int(op["kind"]), int(op["a"]), int(op["b"]), int(op["e1"]),
                                      int(op["e2"]), int(op["slot"]), int(op["mat"]))
     b1 = ext(e1) if e1 >= 0 else None
@@ -194,6 +199,10 @@ def _emit_op(e: _Emitter, op, mats, ext, n_slots: int) -> None:
         e(f"ap_d1<{a}>(v, d);", 2)
     elif kind == sp.K_SLOT:
         e(f"ap_u1<{a}>(v, job_slots + (job * {n_slots} + {slot}) * 8);", 2)
+    elif kind == sp.K_PARAM:
+        # the binding's matrix of param op `slot`: a block-uniform address, read with scalar loads like the
+        # slot table; nothing about it is known at compile time (no scale divided out, nothing snapped)
+        e(f"ap_u1<{a}>(v, bind_mats + (bnd * {n_params} + {slot}) * 8);", 2)
     elif kind == sp.K_U2:
         const_arr("m", [_lit(x) for x in arr(32)])
         e(f"ap_u2<{a}, {b}>(v, m);", 2)
@@ -277,7 +286,17 @@ def _pass_kernel(enc: sp.EncodedProgram, ip: int, name: str, device_fn: bool = F
         e(f'extern "C" __global__ __launch_bounds__({NT}) void {name}(', 0)
     e("const double* __restrict__ job_slots, const double* __restrict__ job_sign,", 2)
     e("double2* __restrict__ state, double* __restrict__ pjob, long long n_jobs,", 2)
-    e("const long long* __restrict__ label_off" + (", const int* __restrict__ pfx) {" if device_fn else ") {"), 2)
+    # bound form (a program with K_PARAM ops): the launch runs n_bind bindings of jobs_per_binding branch jobs
+    # each. A block's unit is b * jobs_per_binding + job: slot matrices and signs by job, param matrices by
+    # binding b (bind_mats[b][p][8]), state rows by unit; n_jobs is then the FINAL rows per binding (labels in
+    # the label form, else jobs) and output row grp = b * n_jobs + row. Programs without K_PARAM ops emit
+    # exactly the unbound text.
+    bound = has_params(enc)
+    if bound and device_fn:
+        raise ValueError("multi-fragment kernels do not take programs with run-time parameters")
+    e("const long long* __restrict__ label_off" + (", const int* __restrict__ pfx) {" if device_fn else
+                                                   ", const double* __restrict__ bind_mats, long long jobs_per_binding) {"
+                                                   if bound else ") {"), 2)
     e("using namespace qk_sweep_ops;")
     if not device_fn:
         e("const int* pfx = nullptr;")
@@ -294,6 +313,8 @@ def _pass_kernel(enc: sp.EncodedProgram, ip: int, name: str, device_fn: bool = F
         e("const unsigned long long tbase = 0ull;")
     e(f"const unsigned long long lo = {_deposit('(unsigned long long)tid', list(range(TB - 4)), bitpos[:TB - 4])};")
     e("(void)n_jobs; (void)job_slots; (void)lo; (void)label_off; (void)pfx;")
+    if bound:
+        e("(void)bind_mats; (void)jobs_per_binding;")
     keep = [i for i in range(PER) if not ((NT * i) & traced)]
     gids = list(range(int(ps["group_begin"]), int(ps["group_end"])))
     zero_tile = init and not init_sparse and tpj_log > 0
@@ -307,13 +328,12 @@ def _pass_kernel(enc: sp.EncodedProgram, ip: int, name: str, device_fn: bool = F
     if gids and not (final and traced):
         return _pass_body_direct(e, enc, ps, gids, TB, NT, n, m, bitpos, init, final, zero_tile, zero_mask)
     if final:
-        e("long long j0 = grp, j1 = grp + 1;")
-        e("if (label_off) { j0 = label_off[grp]; j1 = label_off[grp + 1]; }")
+        _job_range(e, bound)
         for i in keep:
             e(f"double out{i} = 0.0;")
         e("for (long long job = j0; job < j1; ++job) {")
     else:
-        e("const long long job = grp;")
+        _single_job(e, bound)
     e(_state_ptr(enc, ps))
     e("(void)st;")
     if init:
@@ -378,10 +398,35 @@ def _pass_kernel(enc: sp.EncodedProgram, ip: int, name: str, device_fn: bool = F
     return e.lines
 
 
+def _job_range(e: _Emitter, bound: bool) -> None:
+    """FINAL pass: the branch jobs [j0, j1) whose signed probabilities output row ``grp`` sums (bound form:
+    of binding ``bnd``, row ``grp - bnd * n_jobs`` of it)."""
+    if bound:
+        e("const long long bnd = grp / n_jobs;")
+        e("const long long row = grp - bnd * n_jobs;")
+        e("long long j0 = row, j1 = row + 1;")
+        e("if (label_off) { j0 = label_off[row]; j1 = label_off[row + 1]; }")
+    else:
+        e("long long j0 = grp, j1 = grp + 1;")
+        e("if (label_off) { j0 = label_off[grp]; j1 = label_off[grp + 1]; }")
+
+
+def _single_job(e: _Emitter, bound: bool) -> None:
+    """Other passes: the block's one job (bound form: ``grp`` is the unit)."""
+    if bound:
+        e("const long long bnd = grp / jobs_per_binding;")
+        e("const long long job = grp - bnd * jobs_per_binding;")
+    else:
+        e("const long long job = grp;")
+
+
 def _state_ptr(enc, ps) -> str:
     """Job state of a pass: the FINAL pass of a two-pass program may start from a shared INIT
-    prefix's state (``pfx``: job -> prefix slot, qk_sweep_compiled_multi_shared)."""
+    prefix's state (``pfx``: job -> prefix slot, qk_sweep_compiled_multi_shared). Bound form: the
+    state row of the unit."""
     n = enc.n
+    if has_params(enc):
+        return f"double2* st = state + (bnd * jobs_per_binding + job) * {1 << n}ll;"
     if len(enc.passes) == 2 and bool(int(ps["flags"]) & sp.PASS_FINAL):
         return f"double2* st = state + (pfx ? (long long)pfx[job] : job) * {1 << n}ll;"
     return f"double2* st = state + job * {1 << n}ll;"
@@ -409,7 +454,7 @@ def _layout(pos: list, nonfib: list, TB: int, bitpos: list) -> dict:
     }
 
 
-_ONE_Q = (sp.K_U1, sp.K_D1, sp.K_SLOT, sp.K_U1R, sp.K_U1X, sp.K_D1R)
+_ONE_Q = (sp.K_U1, sp.K_D1, sp.K_SLOT, sp.K_U1R, sp.K_U1X, sp.K_D1R, sp.K_PARAM)
 _TWO_Q = (sp.K_U2, sp.K_D2, sp.K_CX, sp.K_SWAP, sp.K_D2R)
 
 
@@ -545,7 +590,7 @@ def _emit_group_ops(e: _Emitter, enc, gi: int, f: dict, bitpos: list) -> None:
             for fld in ("a",) if kind in _ONE_Q else ("a", "b") if kind in _TWO_Q else ():
                 op[fld] = remap[int(op[fld])]
                 assert op[fld] >= 0
-        _emit_op(e, op, enc.mats, ext, enc.n_slots)
+        _emit_op(e, op, enc.mats, ext, enc.n_slots, enc.n_params)
 
 
 def _pass_body_direct(e: _Emitter, enc, ps, gids: list, TB: int, NT: int, n: int, m: int, bitpos: list,
@@ -559,11 +604,10 @@ def _pass_body_direct(e: _Emitter, enc, ps, gids: list, TB: int, NT: int, n: int
         e(f"const unsigned long long xlo = (tbase | {last['lo']}) & 0x{mmask:x}ull;")
         for r in range(PER):
             e(f"double out{r} = 0.0;")
-        e("long long j0 = grp, j1 = grp + 1;")
-        e("if (label_off) { j0 = label_off[grp]; j1 = label_off[grp + 1]; }")
+        _job_range(e, has_params(enc))
         e("for (long long job = j0; job < j1; ++job) {")
     else:
-        e("const long long job = grp;")
+        _single_job(e, has_params(enc))
     loop_start = len(e.lines)
     e(_state_ptr(enc, ps))
     e("(void)st;")

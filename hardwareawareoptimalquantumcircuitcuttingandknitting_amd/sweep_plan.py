@@ -36,7 +36,7 @@ FIBER_BITS = 4
 LOW_BITS = 5  # state bits always resident in a SPLIT tile (512-B contiguous runs)
 
 # op kinds (must match qknit.h)
-K_U1, K_D1, K_SLOT, K_U2, K_D2, K_CX, K_SWAP, K_SCALE, K_U1R, K_U1X, K_D1R, K_D2R, K_SCALER = range(13)
+K_U1, K_D1, K_SLOT, K_U2, K_D2, K_CX, K_SWAP, K_SCALE, K_U1R, K_U1X, K_D1R, K_D2R, K_SCALER, K_PARAM = range(14)
 
 OP_DTYPE = np.dtype([("kind", "<i4"), ("a", "<i4"), ("b", "<i4"), ("e1", "<i4"),
                      ("e2", "<i4"), ("slot", "<i4"), ("mat", "<i4"), ("pad", "<i4")])
@@ -45,6 +45,11 @@ GROUP_DTYPE = np.dtype([("pos", "<i4", (4,)), ("op_begin", "<i4"), ("op_end", "<
 PASS_DTYPE = np.dtype([("tile_mask", "<u8"), ("group_begin", "<i4"), ("group_end", "<i4"),
                        ("flags", "<i4"), ("traced_local", "<u4")])
 PASS_INIT, PASS_FINAL = 1, 2
+PASS_PARAM = 4  # the pass holds K_PARAM ops: only the bound sweep entries may run it (qknit.h QK_PASS_PARAM)
+
+# ops whose 2x2 matrix exists at run time only (per job, per binding): the planner knows nothing about
+# it, so each counts as a non-diagonal one-qubit op wherever it asks what an op does
+RUNTIME_KINDS = ("slot", "param")
 
 
 # ----------------------------------------------------------------------------- analysis
@@ -57,7 +62,7 @@ def _diag_qubits(op: HostOp) -> frozenset:
     """Qubits on which the op acts diagonally (it commutes with Z there). Memoised on the op's
     kind, qubits and matrix bytes: the pass scheduler asks for every op of every candidate tile
     width (syc 32 5: ~8000 queries for ~190 ops)."""
-    if op.kind == "slot":
+    if op.kind in RUNTIME_KINDS:
         return frozenset()
     m = np.asarray(op.mat)
     key = (op.kind, tuple(op.qubits), m.dtype.str, m.shape, m.tobytes())
@@ -90,7 +95,7 @@ def op_need(op: HostOp) -> set:
 def drop_trailing_phases(prog: FragmentProgram) -> FragmentProgram:
     """The program without its trailing phases: a diagonal op whose entries all have modulus 1 and
     after which no op acts non-diagonally on any of its qubits commutes with everything that follows
-    it (later ops on its qubits are diagonal; slot ops count as non-diagonal), so it can move to the
+    it (later ops on its qubits are diagonal; slot and param ops count as non-diagonal), so it can move to the
     end, where it multiplies each amplitude by a unit phase that |z|^2 — every output the sweep makes,
     measured or traced — cannot see. syc 32 5 drops 14 and 7 of its fragments' 94 ops (most from the
     FINAL pass), syc 32 1 10 and 13 of 23, qft 16 105 of 586. ``QKNIT_DROP_PHASES=0`` keeps them."""
@@ -100,10 +105,10 @@ def drop_trailing_phases(prog: FragmentProgram) -> FragmentProgram:
     keep = []
     for op in reversed(prog.ops):
         qs = set(op.qubits)
-        if op.kind != "slot" and op.mat is not None and _diag_qubits(op) >= qs and not (qs & later) \
+        if op.kind not in RUNTIME_KINDS and op.mat is not None and _diag_qubits(op) >= qs and not (qs & later) \
                 and np.all(np.abs(np.abs(np.diag(op.mat)) - 1.0) <= 1e-15):
             continue
-        later |= qs if op.kind == "slot" else op_need(op)
+        later |= qs if op.kind in RUNTIME_KINDS else op_need(op)
         keep.append(op)
     if len(keep) == len(prog.ops):
         return prog
@@ -224,6 +229,7 @@ class EncodedProgram:
     mats: np.ndarray  # float64, interleaved complex
     n_host_ops: int
     tile_bits: int = TILE_BITS  # SPLIT: state bits per tile (12 interpreter; 13 compiled kernels)
+    n_params: int = 0  # param ops (K_PARAM): rows of a binding's matrix table
 
     @property
     def jobs_per_tile(self) -> int:
@@ -301,6 +307,8 @@ def _emit(op: HostOp, fib: dict, mats: _Mats) -> list:
     rec = lambda kind, a=-1, b=-1, e1=-1, e2=-1, slot=-1, mat=-1: (kind, a, b, e1, e2, slot, mat, 0)
     if op.kind == "slot":
         return [rec(K_SLOT, a=fib[op.qubits[0]], slot=op.slot)]
+    if op.kind == "param":  # the `slot` field holds the index into prog.params
+        return [rec(K_PARAM, a=fib[op.qubits[0]], slot=op.slot)]
     if op.kind == "u1":
         q = op.qubits[0]
         m = op.mat
@@ -460,6 +468,8 @@ def encode(prog: FragmentProgram, tile_bits: int = TILE_BITS, final_tile_bits: i
                 ops_out.extend(_emit(op, fib, mats))
             groups_out.append((pos, ob, len(ops_out), (0, 0)))
         flags = (PASS_INIT if pi == 0 else 0) | (PASS_FINAL if pi == len(passes) - 1 else 0)
+        if any(op.kind == "param" for op in p.ops):
+            flags |= PASS_PARAM
         traced = 0
         if flags & PASS_FINAL:
             for q in range(prog.m, n_eff):
@@ -478,4 +488,5 @@ def encode(prog: FragmentProgram, tile_bits: int = TILE_BITS, final_tile_bits: i
     mat_arr = np.asarray(mats.buf if mats.buf else [0.0], dtype=np.float64)
     return EncodedProgram(n=n, n_eff=n_eff, m=prog.m, n_slots=prog.num_slots, packed=packed,
                           ops=ops_arr, groups=grp_arr, passes=pass_arr, mats=mat_arr,
-                          n_host_ops=len(prog.ops), tile_bits=tile_bits)
+                          n_host_ops=len(prog.ops), tile_bits=tile_bits,
+                          n_params=len(getattr(prog, "params", ())))

@@ -129,6 +129,11 @@ class VirtualCircuit:
         """The cut circuit with virtual gates replaced by endpoints."""
         return self._circuit
 
+    @property
+    def parameters(self) -> list:
+        """The circuit's run-time parameters (``QuantumCircuit.parameters``: order of first appearance)."""
+        return list(getattr(self._circuit, "parameters", []))
+
     def replace_fragment_circuit(self, fragment, circuit: QuantumCircuit) -> None:
         self._frag_circs[self._frag(fragment)] = circuit
         self._generation += 1

@@ -47,13 +47,16 @@ extern "C" {
  *   D2R real diag4 (4)   SCALER real scalar (1 per variant).
  * Variant index = bit(e1) + 2*bit(e2) of the thread's fixed state bits (-1: bit taken as 0). */
 enum { QK_U1 = 0, QK_D1 = 1, QK_SLOT = 2, QK_U2 = 3, QK_D2 = 4, QK_CX = 5, QK_SWAP = 6, QK_SCALE = 7,
-       QK_U1R = 8, QK_U1X = 9, QK_D1R = 10, QK_D2R = 11, QK_SCALER = 12 };
+       QK_U1R = 8, QK_U1X = 9, QK_D1R = 10, QK_D2R = 11, QK_SCALER = 12,
+       /* a dense 2x2 read per BINDING at run time (qk_sweep_bound): `a` = fiber position, `slot` = row of
+        * the binding's table bind_mats[b][n_params][8]. Only the bound entries run a program that holds one. */
+       QK_PARAM = 13 };
 
 typedef struct qk_op {      /* 32 bytes */
     int32_t kind;
     int32_t a, b;            /* fiber positions (0..3) */
     int32_t e1, e2;          /* external state bits selecting a variant (-1: none) */
-    int32_t slot;            /* QK_SLOT: slot index into the job's slot table */
+    int32_t slot;            /* QK_SLOT: slot index into the job's slot table; QK_PARAM: param index */
     int32_t mat;             /* offset (doubles) into qk_program.mats */
     int32_t pad;
 } qk_op;
@@ -67,9 +70,12 @@ typedef struct qk_group {   /* 32 bytes: one fiber (4 tile positions) and its op
 typedef struct qk_pass {    /* 24 bytes */
     uint64_t tile_mask;      /* state bits resident in the tile (SPLIT mode) */
     int32_t group_begin, group_end;
-    int32_t flags;           /* 1: INIT (state starts as |0..0>), 2: FINAL (emit probabilities) */
+    int32_t flags;           /* 1: INIT (state starts as |0..0>), 2: FINAL (emit probabilities),
+                              * 4: QK_PASS_PARAM (the pass holds QK_PARAM ops) */
     uint32_t traced_local;   /* FINAL: tile positions that are traced out */
 } qk_pass;
+
+#define QK_PASS_PARAM 4
 
 typedef struct qk_program {
     int32_t n;               /* fragment qubits */
@@ -192,6 +198,30 @@ int qk_sweep_compiled_multi_shared(qk_ctx* ctx, const qk_module* module, int n_p
                                    const int64_t* workspace_bytes, double* const* outs,
                                    const uint64_t* const* block_maps, const int64_t* n_init,
                                    const double* const* init_slots, const int32_t* const* prefix_of);
+
+/* ---- bound sweep: run-time parameters (DESIGN.md §3 "Run-time parameters") ------------------
+ * A program with QK_PARAM ops is swept for n_bind parameter bindings at once. A unit is
+ * u = b * n_jobs + j (binding b, branch job j): its slot matrices and sign are job_slots[j] and
+ * job_sign[j] as in qk_sweep, its param matrices bind_mats[b][p] (DEVICE, [n_bind][n_params][8]
+ * doubles), its state row and (without label offsets) its output row are u.
+ *   module        NULL: the interpreter kernel (12-bit tiles, PACKED or SPLIT; per-unit rows only);
+ *                 else the per-program kernels of sweep_codegen.generate for this program
+ *                 (its bound form: the program must hold a QK_PARAM op).
+ *   ops_host      HOST copy of prog->ops (n_ops entries): checked before any launch.
+ *   label_offsets NULL: out = [n_bind * n_jobs][2^m]; else (module only, DEVICE, n_labels + 1 offsets
+ *                 into ONE binding's jobs) out = [n_bind * n_labels][2^m] as qk_sweep_compiled_labels.
+ * Refused before any launch (QK_EARG): n_bind < 1, n_params < 0, a null bind_mats with n_params > 0,
+ * a workspace below n_bind * n_jobs states, a QK_PARAM op whose index is not below n_params, a
+ * QK_PARAM op in a pass without QK_PASS_PARAM. The unbound entries (qk_sweep, qk_sweep_compiled*,
+ * qk_sweep_compiled_multi*) refuse a program with a QK_PASS_PARAM pass.
+ * qk_sweep_bound_check runs exactly those checks and nothing else (no context, no device). */
+int qk_sweep_bound_workspace_bytes(const qk_program* prog, int64_t n_bind, int64_t n_jobs, int64_t* bytes);
+int qk_sweep_bound_check(const qk_program* prog, const qk_op* ops_host, int64_t n_ops, int64_t n_bind,
+                         int32_t n_params, const double* bind_mats, int64_t n_jobs, int64_t workspace_bytes);
+int qk_sweep_bound(qk_ctx* ctx, const qk_module* module, const qk_program* prog, const qk_op* ops_host,
+                   int64_t n_ops, int64_t n_bind, int32_t n_params, const double* bind_mats, int64_t n_jobs,
+                   const double* job_slots, const double* job_sign, int64_t n_labels,
+                   const int64_t* label_offsets, void* workspace, int64_t workspace_bytes, double* out);
 
 /* q[l][x] = sum_{j in [offsets[l], offsets[l+1])} pjob[j][x]   (offsets: DEVICE, n_labels+1) */
 int qk_reduce_labels(qk_ctx* ctx, int64_t n_labels, const int64_t* offsets, int64_t width,

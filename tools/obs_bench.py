@@ -34,7 +34,8 @@ channels_leg.
 
 ``--projection`` runs the nearest-probability-distribution leg instead (``--out``: e.g.
 profiles/obs_bench_projection.json): see projection_leg. ``--projected`` the projection as a distribution (``--out``:
-profiles/obs_bench_projected.json): see projected_leg."""
+profiles/obs_bench_projected.json): see projected_leg. ``--parametric`` the run-time parameter leg (``--out``:
+profiles/obs_bench_parametric.json): see parametric_leg."""
 import argparse
 import glob
 import json
@@ -810,8 +811,91 @@ def projected_leg(args):
             fh.write("\n")
 
 
+def parametric_leg(args):
+    """Run-time parameters (``--out``: profiles/obs_bench_parametric.json) on the parametric hwea ansatz, 16 qubits
+    cut into 2 x 8 (PACKED programs) and 36 qubits cut into 2 x 18 (SPLIT programs), one cx cut each, depth 1, one
+    process, HIP events, medians of 20: (a) ``ParametricKnit.bind(v)`` against the constant route to the same
+    reducer, ``KnitReducer(VirtualCircuit(cut.bind(v)))`` with a fresh ``v`` per call and an empty jit cache
+    directory (programs of these sizes stay on the interpreter there; with per-program kernels forced,
+    ``prepare_fragments(jit=True)`` plus the sweeps of a fresh ``v``, 3 repeats: every call compiles); (b) per fragment the bound sweep of one binding (``sweep_fragment_bound``) against the constant-folded
+    sweep of the same angles (``sweep_fragment``), interpreter and, for the SPLIT programs, per-program kernels
+    (event windows around the two calls: at these sizes they hold the launches' host side too, and the constant
+    call uploads its job tables each time; kernel-only times need a kernel trace and are not taken here);
+    (c) ``bind_many`` of 64 bindings against 64 ``bind`` calls."""
+    import numpy as np
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine, generators
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.circuit import Parameter
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.observables import KnitReducer
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.parametric import ParametricKnit
+
+    os.environ["QKNIT_JIT_CACHE"] = engine.JIT_CACHE_DIR = tempfile.mkdtemp(prefix="qk_jit_empty_")
+    res = {"device": torch.cuda.get_device_name(0), "reps": 20, "cases": {}}
+    ctx = engine.get_context(0)
+    rng = np.random.default_rng(0)
+    for label, n in (("hwe_16_1_p2", 16), ("hwe_36_1_2x18", 36)):
+        params = [Parameter(f"t{i}") for i in range(2 * n * 2)]
+        qc = cutting.decompose(generators.hwea(n, 1, theta=params))
+        mid = n // 2
+        spec = cutting.CutSpec([list(range(mid)), list(range(mid, n))], cutting.two_qubit_gate_indices(qc, mid - 1, mid)[:1])
+        cut = cutting.cut_circuit(qc, spec)
+        P = len(params)
+        fresh = lambda: rng.uniform(-np.pi, np.pi, P)  # noqa: E731
+        entry = {"qubits": n, "parameters": P}
+        for jit in ((None,) if n == 16 else (None, True)):
+            tag = "default" if jit is None else "jit"
+            pk = ParametricKnit(VirtualCircuit(cut), jit=jit)
+            e = {"fragments": [{"n": fs.prog.n, "ops": len(fs.prog.ops), "param_ops": fs.prog.num_params,
+                                "jobs": fs.jobs.n_jobs, "compiled": fs.dprog.module is not None} for fs in pk.frags]}
+            # (a)
+            e["bind"] = timed(torch, lambda: pk.bind(fresh()))
+            if jit is None:
+                e["constant_route_fresh_values"] = timed(torch, lambda: KnitReducer(VirtualCircuit(cut.bind(fresh()))))
+            else:
+                def constant_compiled():
+                    frags = engine.prepare_fragments(VirtualCircuit(cut.bind(fresh())), 0, basis=True, jit=True)
+                    assert all(f.dprog.module is not None for f in frags)
+                    return [engine.sweep_fragment(ctx, f) for f in frags]
+
+                e["constant_route_compiled_fresh_values"] = timed(torch, constant_compiled, reps=3, warm=0)
+                e["bound_sweeps_fresh_values"] = timed(torch, lambda: pk.sweep(fresh()[None]))
+            # (b): the same angles, swept as a binding and as constants
+            v = fresh()
+            const = engine.prepare_fragments(VirtualCircuit(cut.bind(v)), 0, basis=True, jit=jit)
+            bound_ms = const_ms = 0.0
+            per = []
+            for fs, fc in zip(pk.frags, const):
+                mats = fs.prog.bind_matrices(v[None])
+                tb = timed(torch, lambda: engine.sweep_fragment_bound(ctx, fs, mats))
+                tc = timed(torch, lambda: engine.sweep_fragment(ctx, fc))
+                diff = float((engine.sweep_fragment_bound(ctx, fs, mats)[0] - engine.sweep_fragment(ctx, fc)).abs().max())
+                per.append({"bound": tb, "constant": tc, "constant_ops": len(fc.prog.ops), "max_abs_diff": diff,
+                            "constant_compiled": fc.dprog.module is not None})
+                bound_ms += tb["median_ms"]
+                const_ms += tc["median_ms"]
+            e["sweep_one_binding"] = {"per_fragment": per, "bound_ms": bound_ms, "constant_ms": const_ms,
+                                      "bound_over_constant": bound_ms / const_ms}
+            # (c)
+            V = rng.uniform(-np.pi, np.pi, (64, P))
+            e["bind_many_64"] = timed(torch, lambda: pk.bind_many(V))
+            e["bind_x64"] = timed(torch, lambda: [pk.bind(r) for r in V])
+            e["bind_x64_over_bind_many_64"] = e["bind_x64"]["median_ms"] / e["bind_many_64"]["median_ms"]
+            if jit is None:
+                e["constant_over_bind"] = e["constant_route_fresh_values"]["median_ms"] / e["bind"]["median_ms"]
+            entry[tag] = e
+            print(label, tag, json.dumps(e), flush=True)
+        res["cases"][label] = entry
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--parametric", action="store_true", help="the run-time parameter leg only (see parametric_leg)")
     ap.add_argument("--projection", action="store_true",
                     help="the nearest-probability-distribution leg only (see projection_leg)")
     ap.add_argument("--projected", action="store_true",
@@ -828,6 +912,8 @@ def main():
     args = ap.parse_args()
     if args.shots_child:
         return shots_child()
+    if args.parametric:
+        return parametric_leg(args)
     if args.shots:
         return shots_leg(args)
     if args.spectrum:
