@@ -28,7 +28,8 @@ from .virtual_gates import (
 )
 from .virtual_circuit import VirtualCircuit, generate_instantiations
 from .run import (RunTimeInfo, run_virtual_circuit, run_virtual_circuit_collision, run_virtual_circuit_dense,
-                  run_virtual_circuit_expectation, run_virtual_circuit_fidelity, run_virtual_circuit_marginal,
+                  run_virtual_circuit_expectation, run_virtual_circuit_fidelity, run_virtual_circuit_gradient,
+                  run_virtual_circuit_marginal,
                   run_virtual_circuit_npd,
                   run_virtual_circuit_overlap, run_virtual_circuit_probabilities, run_virtual_circuit_scan,
                   run_virtual_circuit_shots, run_virtual_circuit_top_k, run_virtual_circuit_xeb)
@@ -39,7 +40,8 @@ __all__ = [
     "VIRTUAL_GATE_TYPES", "VirtualBinaryGate", "VirtualCPhase", "VirtualCX", "VirtualCY",
     "VirtualCZ", "VirtualGateEndpoint", "VirtualMove", "VirtualRZZ", "WireCut", "VirtualCircuit",
     "generate_instantiations", "RunTimeInfo", "run_virtual_circuit", "run_virtual_circuit_dense",
-    "run_virtual_circuit_marginal", "run_virtual_circuit_expectation", "run_virtual_circuit_shots",
+    "run_virtual_circuit_marginal", "run_virtual_circuit_expectation", "run_virtual_circuit_gradient",
+    "run_virtual_circuit_shots",
     "run_virtual_circuit_probabilities", "run_virtual_circuit_xeb", "run_virtual_circuit_collision",
     "run_virtual_circuit_overlap", "run_virtual_circuit_scan", "run_virtual_circuit_top_k",
     "run_virtual_circuit_fidelity", "run_virtual_circuit_npd", "Parameter", "ParametricKnit",

@@ -146,6 +146,8 @@ SIGNATURES = {
                                c_vp, c_i64]),
     "qk_wht_rows": (c_i32, [c_vp, c_i64, ctypes.c_int, c_vp, c_i64, c_vp, c_i64]),
     "qk_kron2_rows": (c_i32, [c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_i64]),
+    "qk_rows_dot_workspace_bytes": (c_i32, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "qk_rows_dot": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64]),
     "qk_uniforms": (c_i32, [c_vp, c_u64, c_i64, c_i64, c_i64, c_vp]),
     "qk_sample_rows_workspace_bytes": (c_i32, [c_i64, ctypes.c_int, ctypes.POINTER(c_i64)]),
     "qk_sample_rows": (c_i32, [c_vp, c_i64, ctypes.c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,

@@ -14,7 +14,8 @@ SRCS = [os.path.join(HERE, "csrc", f) for f in ("qknit.hip", "qknit_post.hip", "
                                                               "qknit_prim.hip", "qknit_obs.hip",
                                                               "qknit_shots.hip", "qknit_wht.hip",
                                                               "qknit_lookup.hip", "qknit_moments.hip",
-                                                              "qknit_scan.hip", "qknit_kron.hip")]
+                                                              "qknit_scan.hip", "qknit_kron.hip",
+                                                              "qknit_dot.hip")]
 DEPS = SRCS + [os.path.join(HERE, "csrc", h) for h in ("internal.h", "sweep_ops.h", "prim.h", "rng.h",
                                                                 "wh_tile.h", "kron_plan.h")]
 HEADER = os.path.join(os.path.dirname(HERE), "include", "qknit.h")

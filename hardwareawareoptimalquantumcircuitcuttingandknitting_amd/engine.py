@@ -774,6 +774,38 @@ def kron2_rows(ctx: Context, src, mats, m: int | None = None, out=None):
     return out
 
 
+def rows_dot(ctx: Context, Q, D, per: int = 1, out=None):
+    """``qk_rows_dot``: ``out[u] = sum over i < n of Q[u, i] * D[u // per, i]`` -> float64 ``[units]``. ``Q``: float64
+    ``[units, n]`` and ``D``: float64 ``[units / per, n]`` on one device, each with unit column stride (any row
+    stride ``>= n``, any 8-byte aligned base); both are only read. Deterministic, and a unit's bits depend on
+    ``n`` alone: not on ``units``, ``per`` or the units launched with it. ``out`` (optional): a contiguous
+    float64 ``[units]`` on the same device."""
+    T = torch()
+    per = int(per)
+    if per < 1:
+        raise ValueError(f"per must be at least 1, not {per}")
+    for name, X in (("Q", Q), ("D", D)):
+        if X.dim() != 2 or X.dtype != T.float64 or not X.is_cuda or X.shape[1] < 1 or (X.shape[1] > 1 and X.stride(1) != 1):
+            raise ValueError(f"{name} must be a device float64 [rows, n >= 1] with unit column stride")
+    units, n = Q.shape
+    if D.device != Q.device or D.shape[1] != n or D.shape[0] * per != units:
+        raise ValueError(f"Q {list(Q.shape)} and D {list(D.shape)} do not fit per = {per} on one device")
+    ldq = Q.stride(0) if units > 1 else max(Q.stride(0), n)
+    ldd = D.stride(0) if D.shape[0] > 1 else max(D.stride(0), n)
+    if ldq < n or ldd < n:
+        raise ValueError("row stride of Q or D below n")
+    if out is None:
+        out = T.empty(units, dtype=T.float64, device=Q.device)
+    if out.shape != (units,) or out.dtype != T.float64 or out.device != Q.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float64 [{units}] on the device of Q")
+    if units == 0:
+        return out
+    work, work_bytes = _workspace(ctx, "qk_rows_dot_workspace_bytes", units, n, device=Q.device)
+    ctx.check(ctx.lib.qk_rows_dot(ctx.handle, units, per, n, Q.data_ptr(), ldq, D.data_ptr(), ldd, out.data_ptr(),
+                                  _ptr(work), work_bytes), "qk_rows_dot")
+    return out
+
+
 KNIT_AT_MAX_FRAGMENTS = 16  # QK_KNIT_AT_MAX_FRAGMENTS
 
 
@@ -1626,6 +1658,7 @@ def sweep_fragment(ctx: Context, fs: FragmentState, label_range=None):
 
 
 BOUND_WORKSPACE_BYTES = 1 << 30  # state workspace of one bound sweep launch: more bindings go in chunks
+GRADIENT_ROW_BYTES = 1 << 30  # shifted rows a gradient holds at a time: more (binding, occurrence) pairs go in chunks
 
 
 def binding_chunks(n_bind: int, unit_bytes: int, budget: int) -> list:

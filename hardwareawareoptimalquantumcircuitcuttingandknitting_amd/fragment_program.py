@@ -92,17 +92,90 @@ class FragmentProgram:
         column = {p: i for i, p in enumerate(self.parameters)}
         out = np.empty((B, len(self.params), 2, 2), dtype=np.complex128)
         for k, op in enumerate(self.params):
-            acc = None
-            for f in op.factors:
-                if isinstance(f, np.ndarray):
-                    m = np.broadcast_to(f, (B, 2, 2))
-                else:
-                    name, angles = f
-                    m = _g.gate_matrix_batch(name, [a.evaluate_batch(values, column) if isinstance(a, ParameterExpression)
-                                                    else np.full(B, float(a)) for a in angles])
-                acc = m if acc is None else np.matmul(m, acc)
-            out[:, k] = acc
+            out[:, k] = self._param_matrix(op, values, column)
         return out
+
+    @staticmethod
+    def _param_matrix(op: HostOp, values: np.ndarray, column: dict, occ: "ShiftOccurrence | None" = None,
+                      delta: float = 0.0) -> np.ndarray:
+        """``[B, 2, 2]``: the product of a param op's factors at ``values``; with ``occ`` (an occurrence of this
+        op) that one angle occurrence moved by ``delta``."""
+        B = values.shape[0]
+        acc = None
+        for j, f in enumerate(op.factors):
+            if isinstance(f, np.ndarray):
+                m = np.broadcast_to(f, (B, 2, 2))
+            else:
+                name, angles = f
+                vals = [a.evaluate_batch(values, column) if isinstance(a, ParameterExpression)
+                        else np.full(B, float(a)) for a in angles]
+                if occ is not None and occ.factor == j and occ.side == 0:
+                    vals[occ.angle] = vals[occ.angle] + delta
+                m = _g.gate_matrix_batch(name, vals)
+                if occ is not None and occ.factor == j and occ.side != 0:
+                    # r(theta, phi) = rz(phi) rx(theta) rz(-phi): the left (+1) or the right (-1) rotation moved
+                    rz = _g.gate_matrix_batch("rz", [np.full(B, float(delta))])
+                    m = np.matmul(rz, m) if occ.side > 0 else np.matmul(m, rz)
+            acc = m if acc is None else np.matmul(m, acc)
+        return acc
+
+    def shift_occurrences(self) -> list:
+        """The angle occurrences a parameter-shift gradient moves, in program order (param op, factor, angle):
+        one :class:`ShiftOccurrence` per angle slot of a param op's factors that holds an expression with a
+        non-zero term. ``rx ry rz p u1``, every angle of ``u2 u3 u`` and ``theta`` of ``r`` enter through one
+        rotation whose generator has eigenvalues +-1/2, so the two-term rule with shift pi/2 and factor 1/2
+        holds for the slot as it stands. ``phi`` of ``r`` enters two rotations (``r = rz(phi) rx(theta) rz(-phi)``)
+        and gives two occurrences, the left one with the slot's coefficients and the right one with their
+        negatives; the program the kernels run is not changed."""
+        column = {p: i for i, p in enumerate(self.parameters)}
+        out = []
+        for k, op in enumerate(self.params):
+            for j, f in enumerate(op.factors):
+                if isinstance(f, np.ndarray):
+                    continue
+                name, angles = f
+                for a, expr in enumerate(angles):
+                    if not isinstance(expr, ParameterExpression):
+                        continue
+                    coefs = {column[p]: float(c) for p, c in expr.terms.items() if c != 0.0}
+                    if not coefs:
+                        continue
+                    if name == "r" and a == 1:
+                        out.append(ShiftOccurrence(k, j, a, coefs, 1))
+                        out.append(ShiftOccurrence(k, j, a, {p: -c for p, c in coefs.items()}, -1))
+                    else:
+                        out.append(ShiftOccurrence(k, j, a, coefs))
+        return out
+
+    def bind_matrices_shifted(self, values, occurrences) -> np.ndarray:
+        """complex128 ``[B, len(occurrences), 2, num_params, 2, 2]``: for every binding, occurrence and sign
+        (index 0: ``+pi/2``, 1: ``-pi/2``) the table of :meth:`bind_matrices` with the occurrence's op recomputed at
+        its angle moved by the shift; every other matrix is the binding's own. Host work, vectorised over the
+        bindings; ``occurrences`` may be any slice of :meth:`shift_occurrences`."""
+        base = self.bind_matrices(values)
+        values = np.asarray(values, dtype=np.float64)
+        B, K = base.shape[:2]
+        column = {p: i for i, p in enumerate(self.parameters)}
+        out = np.empty((B, len(occurrences), 2, K, 2, 2), dtype=np.complex128)
+        out[:] = base[:, None, None]
+        for o, occ in enumerate(occurrences):
+            for s, delta in enumerate((0.5 * np.pi, -0.5 * np.pi)):
+                out[:, o, s, occ.op] = self._param_matrix(self.params[occ.op], values, column, occ, delta)
+        return out
+
+
+@dataclass(frozen=True)
+class ShiftOccurrence:
+    """One angle occurrence of a fragment program (:meth:`FragmentProgram.shift_occurrences`): the param op
+    (index into ``prog.params``), the factor of its run, the angle of that factor, and the angle's derivative
+    ``{parameter column: coefficient}``. ``side``: 0 for an angle that is one rotation; +1 / -1 for the left /
+    right ``rz`` of ``r``'s ``phi``."""
+
+    op: int
+    factor: int
+    angle: int
+    coefs: dict
+    side: int = 0
 
 
 def _op_matrix(op) -> np.ndarray:

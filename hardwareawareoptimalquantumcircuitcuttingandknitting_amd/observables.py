@@ -302,6 +302,62 @@ def kron2_host(src, m: int, mats) -> np.ndarray:
     return x
 
 
+ROWS_DOT_SEGMENT = 8192  # qknit_dot.hip: elements per (unit, segment) workgroup of qk_rows_dot
+
+
+def rows_dot_chain(n: int) -> int:
+    """The longest chain of additions an element passes through in ``qk_rows_dot`` at ``n`` elements per unit
+    (qknit_dot.hip): 16 fused multiply-adds per accumulator, even + odd, a 6-level wave tree and 3 adds of the
+    four wave sums in a segment; then ``ceil(segments / 64)`` lane-strided adds and the tree again."""
+    nseg = -(-int(n) // ROWS_DOT_SEGMENT)
+    return (16 + 1 + 6 + 3) + (-(-nseg // 64) + 6)
+
+
+def rows_dot_host(Q, D, per: int = 1) -> np.ndarray:
+    """numpy model of ``qk_rows_dot``: ``out[u] = sum_i Q[u, i] * D[u // per, i]`` for ``Q [units, n]`` and
+    ``D [units / per, n]`` (numpy's pairwise summation; the kernel's own fixed order differs in the last bits)."""
+    Q, D = np.asarray(Q, dtype=np.float64), np.asarray(D, dtype=np.float64)
+    per = int(per)
+    if Q.ndim != 2 or D.ndim != 2 or per < 1 or Q.shape[0] != D.shape[0] * per or Q.shape[1] != D.shape[1]:
+        raise ValueError(f"Q {Q.shape} and D {D.shape} do not fit per = {per}")
+    return np.einsum("dpi,di->dp", Q.reshape(D.shape[0], per, Q.shape[1]), D).reshape(-1)
+
+
+def cotangent_scatter_host(C: np.ndarray, local_masks: list) -> tuple:
+    """``(distinct masks ascending, C @ G)``: the columns of ``C [..., M]`` (one per Z string) summed onto the
+    distinct values of ``local_masks`` by the 0/1 matrix ``G [M, distinct]``. Several strings may coincide on one
+    fragment; the matmul combines them in one fixed order, where a scatter-add would not."""
+    uniq = sorted(set(int(z) for z in local_masks))
+    col = {z: j for j, z in enumerate(uniq)}
+    G = np.zeros((len(local_masks), len(uniq)))
+    G[np.arange(len(local_masks)), [col[int(z)] for z in local_masks]] = 1.0
+    return uniq, np.matmul(C, G)
+
+
+def cotangent_rows_host(Ws: list, qs: list, local: list, w) -> list:
+    """numpy model of ``ParametricKnit.cotangent_rows``: per fragment ``D_f [rows_f, 2^m_f]`` with
+    ``<D_f, q_f> = E_w = sum_m w[m] sum_t prod_f X_f[t, m]``, ``X_f = W_f^T red_f`` and ``red_f[r, m] = sum_x
+    (-1)^popcount(x & local[f][m]) q_f[r, x]``. ``Ws[f]``: ``[rows_f, terms]``; ``qs[f]``: ``[rows_f, 2^m_f]``;
+    ``local[f]``: the ``M`` masks restricted to fragment ``f``. ``D_f = wht(scatter(W_f (prod_{f' != f} X_f' * w)))``."""
+    w = np.asarray(w, dtype=np.float64)
+    X = []
+    for W, q, fl in zip(Ws, qs, local):
+        x = np.arange(q.shape[1])
+        signs = np.stack([1.0 - 2.0 * (popcount(x & int(z)) & 1) for z in fl], axis=1)  # [2^m, M]
+        X.append(W.T @ (q @ signs))
+    out = []
+    for f, (W, q, fl) in enumerate(zip(Ws, qs, local)):
+        prod = np.ones_like(X[f])
+        for g, xg in enumerate(X):
+            if g != f:
+                prod = prod * xg
+        uniq, Cu = cotangent_scatter_host(W @ (prod * w[None, :]), fl)
+        D = np.zeros(q.shape)
+        D[:, uniq] = Cu
+        out.append(wht_host(D, q.shape[1].bit_length() - 1))
+    return out
+
+
 def readout_matrix(e0: float, e1: float) -> np.ndarray:
     """The confusion matrix ``[[1 - e0, e1], [e0, 1 - e1]]`` of one clbit: ``A[y][x]`` is the probability of
     reading ``y`` when the bit is ``x``, ``e0 = P(read 1 | 0)`` and ``e1 = P(read 0 | 1)``, both in [0, 1]."""

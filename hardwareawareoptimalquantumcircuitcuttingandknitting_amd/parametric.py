@@ -18,7 +18,7 @@ import numpy as np
 from . import engine
 from .backend import MI355XBackend
 from .knit_plan import LabelSpace
-from .observables import MAX_CLBITS, KnitReducer, parse_masks, split_mask
+from .observables import MAX_CLBITS, KnitReducer, cotangent_scatter_host, parse_masks, split_mask
 
 
 def binding_values(parameters: list, values, *, batch: bool) -> np.ndarray:
@@ -155,6 +155,183 @@ class ParametricKnit:
                     prod = prod * a
                 out[b] = prod.sum(0).cpu().numpy()
         return out if w is None else out @ w
+
+    # -- gradients ------------------------------------------------------------------------------
+    def _weights(self, weights, M: int):
+        if weights is None:
+            return None
+        w = np.asarray(weights.cpu() if hasattr(weights, "cpu") else weights, dtype=np.float64)
+        if w.ndim != 1 or len(w) != M:
+            raise ValueError(f"{M} masks but weights of shape {w.shape}")
+        return w
+
+    def _columns(self, parameters) -> list:
+        """Columns of ``self.parameters`` for ``parameters`` (None: all, in order); an unknown parameter or one
+        named twice is a ``ValueError``."""
+        if parameters is None:
+            return list(range(len(self.parameters)))
+        index = {p: i for i, p in enumerate(self.parameters)}
+        unknown = [getattr(p, "name", p) for p in parameters if p not in index]
+        if unknown or len(set(parameters)) != len(parameters):
+            raise ValueError(f"parameters: unknown {unknown}" if unknown else "parameters: one parameter named twice")
+        return [index[p] for p in parameters]
+
+    def _transform(self, i: int) -> np.ndarray:
+        """``W_f`` ``[swept rows, terms]`` of fragment ``i``: ``X_f = W_f^T red_f`` (``engine.plan_transforms``)."""
+        ops, fs = self._template.ops, self.frags[i]
+        if ops.transforms[i] is not None:
+            return np.ascontiguousarray(ops.transforms[i].T)
+        W = np.zeros((fs.n_rows, ops.num_terms))
+        np.add.at(W, (ops.rows[i], np.arange(ops.num_terms)), ops.coefs[i])
+        return W
+
+    def _base(self, qs: list, B: int, zs: list):
+        """From the swept rows of ``B`` bindings: per fragment the local masks and ``X_f [B, terms, M]`` on the
+        device (``engine.fragment_operands`` per binding, as :meth:`expectation_of_rows` takes them), and the
+        unweighted values ``[B, M]`` in that method's own order of operations."""
+        T = engine.torch()
+        t = self._template
+        M = len(zs)
+        local = [list(col) for col in zip(*(split_mask(z, t.clbits) for z in zs))]
+        reds = []
+        for q, fcl, fl in zip(qs, t.clbits, local):
+            rows, width = q.shape[1], q.shape[2]
+            reds.append(engine.reduce_bits(self.ctx, q.reshape(B * rows, width), len(fcl), 0, fl).view(B, rows, M))
+        per_b = [engine.fragment_operands(self.ctx, t.ops, [r[b] for r in reds]) for b in range(B)]
+        X = [T.stack([per_b[b][f] for b in range(B)]) for f in range(len(qs))]
+        out = np.zeros((B, M))
+        for b in range(B):
+            prod = per_b[b][0]
+            for a in per_b[b][1:]:
+                prod = prod * a
+            out[b] = prod.sum(0).cpu().numpy()
+        return local, X, out
+
+    @staticmethod
+    def _others(X: list, f: int):
+        """``prod over f' != f of X_f'`` in fragment order (all ones for a single fragment)."""
+        prod = None
+        for g, x in enumerate(X):
+            if g != f:
+                prod = x if prod is None else prod * x
+        return X[f] * 0.0 + 1.0 if prod is None else prod
+
+    def _cotangent(self, f: int, q_shape: tuple, Xh: list, local_f: list, w: np.ndarray):
+        """``D_f [B, rows_f, 2^m_f]`` on the device from the host copies ``Xh`` of every ``X_f'``: ``C_f = W_f (prod of
+        the others * w)`` on the host (numpy, one fixed order), masks that coincide on this fragment combined by a
+        0/1 matrix, the result scattered to the distinct masks' columns and transformed by one ``qk_wht_rows``."""
+        T = engine.torch()
+        B, rows, width = q_shape
+        C = np.matmul(self._transform(f)[None], self._others(Xh, f) * w[None, None, :])  # [B, rows, M]
+        uniq, Cu = cotangent_scatter_host(C, local_f)
+        dev = T.device("cuda", self.device)
+        Cu = T.from_numpy(np.ascontiguousarray(Cu).reshape(B * rows, len(uniq))).to(dev)
+        D = T.zeros((B * rows, width), dtype=T.float64, device=dev)
+        D[:, T.tensor(uniq, dtype=T.int64, device=dev)] = Cu  # distinct columns: no accumulation
+        engine.wht_rows(self.ctx, D, out=D)
+        return D.view(B, rows, width)
+
+    def cotangent_rows(self, qs_b: list, masks, weights) -> list:
+        """Per fragment the device tensor ``D_f [rows_f, 2^m_f]`` with ``<D_f, q_f> = E_w``: the cotangent of the
+        weighted sum ``E_w = sum_m weights[m] <Z_masks[m]>`` with respect to fragment ``f``'s swept rows, at the one
+        binding whose rows ``qs_b`` (:meth:`sweep`, one binding) are. ``E_w`` is linear in each fragment's rows, so
+        ``D_f`` does not depend on ``q_f`` itself."""
+        self.ctx.bind_stream()
+        zs = parse_masks(masks, self._template.N)
+        w = self._weights(weights, len(zs))
+        if w is None:
+            raise ValueError("cotangent_rows needs weights (one-hot weights give a single mask's)")
+        if not self.frags or not zs:
+            return [engine.torch().zeros_like(q) for q in qs_b]
+        qs = [q.unsqueeze(0) for q in qs_b]
+        local, X, _ = self._base(qs, 1, zs)
+        Xh = [x.cpu().numpy() for x in X]
+        return [self._cotangent(f, tuple(q.shape), Xh, local[f], w)[0] for f, q in enumerate(qs)]
+
+    @staticmethod
+    def shift_chunks(B: int, n_occ: int, unit_bytes: int, budget: int) -> list:
+        """``[(b0, b1, o0, o1), ...]``: (bindings x occurrences) blocks whose ``2 * (b1 - b0) * (o1 - o0)`` shifted
+        units of ``unit_bytes`` each stay within ``budget`` (at least one pair per block): whole bindings while
+        one fits, else slices of one binding's occurrences."""
+        pairs = max(1, int(budget) // max(2 * int(unit_bytes), 1))
+        if pairs >= n_occ:
+            nb = pairs // n_occ
+            return [(b, min(b + nb, B), 0, n_occ) for b in range(0, B, nb)]
+        return [(b, b + 1, o, min(o + pairs, n_occ)) for b in range(B) for o in range(0, n_occ, pairs)]
+
+    def value_and_gradient(self, values, masks, weights=None, *, parameters=None, row_budget: int | None = None) -> tuple:
+        """The Z-string expectation values of :meth:`expectation` and their exact parameter-shift gradient.
+
+        With ``weights [M]``: ``(E_w [B], grad [B, P'])`` of the weighted sum, by the cotangent route: one batched
+        base sweep gives the value and, per fragment, the cotangent ``D_f`` of ``E_w`` with respect to its rows;
+        each angle occurrence of a fragment is then swept at ``+-pi/2`` (that fragment alone, as ordinary bindings
+        of the bound sweep with one matrix of the table changed) and ``qk_rows_dot`` takes ``<D_f, Q>`` of the
+        shifted rows: ``d E_w / d angle = (dot+ - dot-) / 2``, whatever ``M`` is. Without ``weights``:
+        ``(E [B, M], grad [B, M, P'])`` per mask, by the reduce route (``qk_reduce_bits`` on the shifted rows,
+        knitted against the other fragments' base operands). ``grad[..., j]`` is the derivative with respect to
+        ``parameters[j]`` (a list of this circuit's ``Parameter``; default all, in :attr:`parameters` order): the
+        sum over the occurrences of ``coefficient * occurrence derivative``, in program order on the host, so a
+        parameter that occurs several times or inside an affine expression is differentiated correctly.
+        ``row_budget``: bytes of shifted rows held at a time (``engine.GRADIENT_ROW_BYTES``); more go in chunks,
+        with the same bits on the cotangent route."""
+        T = engine.torch()
+        t = self._template
+        vals = binding_values(self.parameters, values, batch=True)
+        zs = parse_masks(masks, t.N)
+        B, M = len(vals), len(zs)
+        w = self._weights(weights, M)
+        cols = self._columns(parameters)
+        where = {c: j for j, c in enumerate(cols)}
+        budget = engine.GRADIENT_ROW_BYTES if row_budget is None else int(row_budget)
+        if budget < 1:
+            raise ValueError("row_budget must be positive")
+        grad = np.zeros((B, len(cols)) if w is not None else (B, M, len(cols)))
+        if not B or not M or not t.frags:
+            E = np.zeros((B, M))
+            if B and M:
+                E[:] = t._scalar
+            return (E if w is None else E @ w), grad
+        self.ctx.bind_stream()
+        qs = self.sweep(vals)
+        local, X, E = self._base(qs, B, zs)
+        Xh = [x.cpu().numpy() for x in X] if w is not None else None
+        for f, fs in enumerate(self.frags):
+            if fs.dropped or not fs.prog.num_params:
+                continue
+            occs = [o for o in fs.prog.shift_occurrences() if any(c in where for c in o.coefs)]
+            if not occs:
+                continue
+            _, rows, width = qs[f].shape
+            n = rows * width
+            if w is not None:
+                D = self._cotangent(f, (B, rows, width), Xh, local[f], w).view(B, n)
+                d_occ = np.zeros((B, len(occs)))
+            else:
+                Wt = T.from_numpy(np.ascontiguousarray(self._transform(f).T)).to(qs[f].device)  # [terms, rows]
+                Y = self._others(X, f)  # [B, terms, M]
+                d_occ = np.zeros((B, len(occs), M))
+            for b0, b1, o0, o1 in self.shift_chunks(B, len(occs), n * 8, budget):
+                nb, no = b1 - b0, o1 - o0
+                mats = fs.prog.bind_matrices_shifted(vals[b0:b1], occs[o0:o1])
+                Q = engine.sweep_fragment_bound(self.ctx, fs, mats.reshape(nb * no * 2, fs.prog.num_params, 2, 2))
+                if w is not None:
+                    dots = engine.rows_dot(self.ctx, Q.view(nb * no * 2, n), D[b0:b1], per=2 * no)
+                    dots = dots.cpu().numpy().reshape(nb, no, 2)
+                else:
+                    red = engine.reduce_bits(self.ctx, Q.view(nb * no * 2 * rows, width), len(t.clbits[f]), 0, local[f])
+                    Xs = T.matmul(Wt, red.view(nb, no * 2, rows, M))  # [nb, 2 no, terms, M]
+                    dots = (Xs * Y[b0:b1, None]).sum(2).cpu().numpy().reshape(nb, no, 2, M)
+                del Q
+                d_occ[b0:b1, o0:o1] = 0.5 * (dots[:, :, 0] - dots[:, :, 1])
+            for o, occ in enumerate(occs):  # host, in occurrence order
+                for c, coef in occ.coefs.items():
+                    if c in where:
+                        grad[..., where[c]] += coef * d_occ[:, o]
+        return (E if w is None else E @ w), grad
+
+    def gradient(self, values, masks, weights=None, **kw) -> np.ndarray:
+        """The gradient of :meth:`value_and_gradient` alone."""
+        return self.value_and_gradient(values, masks, weights, **kw)[1]
 
 
 # ---------------------------------------------------------------------------- cached plans

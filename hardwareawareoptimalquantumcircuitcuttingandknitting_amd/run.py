@@ -636,6 +636,33 @@ def _bound_expectation(virt: VirtualCircuit, observables, bindings, device: int,
     return out, info
 
 
+def run_virtual_circuit_gradient(virt: VirtualCircuit, observables, bindings, *, weights=None, parameters=None,
+                                 device: int = 0, factored: bool | None = None):
+    """Z-string expectation values of a parametric cut circuit and their exact parameter-shift gradient at every
+    binding (``bindings`` as for :func:`run_virtual_circuit_expectation`): ``((values, grads), RunTimeInfo)``. With
+    ``weights [M]`` the weighted sum, ``values [B]`` and ``grads [B, P']``, by the cotangent route of
+    :meth:`parametric.ParametricKnit.value_and_gradient`; without, ``values [B, M]`` and ``grads [B, M, P']`` per
+    observable. ``parameters``: the ``Parameter`` s to differentiate by (default ``virt.parameters``, in order). The
+    plan is the cached :class:`parametric.ParametricKnit` of the circuit's structure, so a second call compiles
+    nothing; ``run_time`` is the whole evaluation (sweeps, dots and the knit's small algebra are interleaved).
+    One GPU, the exact knit, as ``bindings=`` there."""
+    from . import parametric
+
+    vals = parametric.binding_values(virt.parameters, bindings, batch=True)
+    now = perf_counter()
+    knit = parametric.cached_knit(virt, device, factored)
+    if parameters is not None:  # the caller's Parameter objects, by position, as the cached plan knows them
+        index = {p: i for i, p in enumerate(virt.parameters)}
+        unknown = [getattr(p, "name", p) for p in parameters if p not in index]
+        if unknown:
+            raise ValueError(f"parameters: unknown {unknown}")
+        parameters = [knit.parameters[index[p]] for p in parameters]
+    out = knit.value_and_gradient(vals, observables, weights, parameters=parameters)
+    _sync(device)
+    info = RunTimeInfo(perf_counter() - now, 0.0)
+    return out, info
+
+
 def run_virtual_circuit_shots(virt: VirtualCircuit, shots: int = 20000, *, seed: int = 0, clbits=None,
                               memory: bool = False, device: int = 0, factored: bool | None = None, group=None,
                               sample: bool = False, readout=None, mitigate: bool = False, npd: bool = False,

@@ -545,6 +545,23 @@ int qk_reduce_bits(qk_ctx* ctx, int64_t rows, int m, const double* src, int64_t 
  * the in-place and out-of-place forms agree bit for bit. */
 int qk_wht_rows(qk_ctx* ctx, int64_t rows, int m, const double* src, int64_t ld_src, double* dst, int64_t ld_dst);
 
+/* ---- batched dot of rows with a cotangent (qknit_dot.hip): the per-shift work of a gradient ---------
+ * out[u] = sum over i in [0, n) of Q[u * ldq + i] * D[(u / per) * ldd + i]            for u < units
+ * `per` consecutive units share one row of D (a parameter-shift gradient: the 2 * occurrences shifted
+ * rows of one binding against that binding's cotangent). units >= 0, per >= 1, units % per == 0, n >= 1,
+ * ldq >= n, ldd >= n; Q / D / out / ws are 8-byte aligned DEVICE pointers, ws of at least
+ * qk_rows_dot_workspace_bytes(units, n) bytes (units * ceil(n / 8192) doubles). Anything else is
+ * QK_EARG before any launch; units == 0 is a no-op. Two launches: one workgroup per (unit, segment of
+ * 8192 elements) stores a partial in ws, then one wave per unit sums its partials. Deterministic: no
+ * atomics, and the association is fixed by n alone (per thread one fma chain over its even and one over
+ * its odd elements, a 64-lane shuffle tree, four wave sums in order, the partials lane-strided in index
+ * order and the same tree), so a unit's bits do not depend on units, per, the grid or the units beside
+ * it. Operands whose base and leading dimension are multiples of 16 bytes are read by 16-byte loads,
+ * others by 8-byte loads, with the same bits. */
+int qk_rows_dot_workspace_bytes(int64_t units, int64_t n, int64_t* bytes);
+int qk_rows_dot(qk_ctx* ctx, int64_t units, int64_t per, int64_t n, const double* Q, int64_t ldq, const double* D,
+                int64_t ldd, double* out, void* ws, int64_t ws_bytes);
+
 /* ---- a 2x2 matrix per outcome bit on every row (qknit_kron.hip): per-clbit channels, e.g. readout error ---
  * dst[r * ld_dst + y] = sum over x in [0, 2^m) of prod_{b < m} coef[b][2 * y_b + x_b] * src[r * ld_src + x]
  * for r < rows, y < 2^m: the Kronecker product of m real 2x2 matrices applied to every row, coef[b] =

@@ -35,7 +35,8 @@ channels_leg.
 ``--projection`` runs the nearest-probability-distribution leg instead (``--out``: e.g.
 profiles/obs_bench_projection.json): see projection_leg. ``--projected`` the projection as a distribution (``--out``:
 profiles/obs_bench_projected.json): see projected_leg. ``--parametric`` the run-time parameter leg (``--out``:
-profiles/obs_bench_parametric.json): see parametric_leg."""
+profiles/obs_bench_parametric.json): see parametric_leg. ``--gradient`` the parameter-shift gradient leg (``--out``:
+profiles/obs_bench_gradient.json): see gradient_leg."""
 import argparse
 import glob
 import json
@@ -893,8 +894,119 @@ def parametric_leg(args):
             fh.write("\n")
 
 
+def alternated(torch, routes: dict, rounds: int) -> dict:
+    """Each route of ``routes`` (name -> callable) once per round, the rounds taking the routes in turn, after one
+    untimed pass: per route the median of the rounds and their spread (HIP events around the call, host side
+    included: every route ends by reading its result back)."""
+    for fn in routes.values():
+        fn()
+    ms = {name: [] for name in routes}
+    for _ in range(rounds):
+        for name, fn in routes.items():
+            ms[name].append(timed(torch, fn, reps=1, warm=0)["median_ms"])
+    out = {}
+    for name, t in ms.items():
+        t.sort()
+        out[name] = {"median_ms": t[len(t) // 2], "min_ms": t[0], "max_ms": t[-1], "spread_ms": t[-1] - t[0]}
+    return out
+
+
+GRADIENT_BASELINE_MAX_BYTES = 48 << 30  # rows the 2P whole-circuit shifted bindings of the baseline may hold
+
+
+def gradient_leg(args):
+    """Parameter-shift gradients (``--out``: profiles/obs_bench_gradient.json) on the circuits of
+    :func:`parametric_leg`, the parametric hwea ansatz of 16 qubits cut into 2 x 8 and of 36 qubits cut into 2 x 18,
+    with random Z strings and random weights, M in {1, 64, 1024} and B in {1, 16}. End to end, routes alternated per
+    round (5 rounds at 16 qubits, 3 at 36), median and spread: ``value_and_gradient`` by the cotangent route
+    (weights) and by the reduce route (per mask, then weighted on the host), and what there was before:
+    ``ParametricKnit.expectation`` at the ``2 P`` whole-circuit shifted bindings of every binding (valid here: every
+    ansatz parameter is one angle), skipped where those bindings' rows would exceed GRADIENT_BASELINE_MAX_BYTES.
+    Then, for the first chunk of the wider fragment at B = 16, ``qk_rows_dot`` alone (20 launches, GB/s of the
+    shifted rows and the cotangents read) beside the bound sweep that made the chunk's rows."""
+    import numpy as np
+    import torch
+
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd import VirtualCircuit, cutting, engine, generators
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.circuit import Parameter
+    from hardwareawareoptimalquantumcircuitcuttingandknitting_amd.parametric import ParametricKnit
+
+    res = {"device": torch.cuda.get_device_name(0), "cases": {}}
+    ctx = engine.get_context(0)
+    rng = np.random.default_rng(0)
+    prng = random.Random(0)
+    for label, n, rounds in (("hwe_16_1_p2", 16, 5), ("hwe_36_1_2x18", 36, 3)):
+        params = [Parameter(f"t{i}") for i in range(2 * n * 2)]
+        qc = cutting.decompose(generators.hwea(n, 1, theta=params))
+        mid = n // 2
+        spec = cutting.CutSpec([list(range(mid)), list(range(mid, n))], cutting.two_qubit_gate_indices(qc, mid - 1, mid)[:1])
+        pk = ParametricKnit(VirtualCircuit(cutting.cut_circuit(qc, spec)))
+        P = pk.num_parameters
+        shapes = [tuple(q.shape[1:]) for q in pk.sweep(np.zeros((1, P)))]
+        occs = [len(fs.prog.shift_occurrences()) for fs in pk.frags]
+        entry = {"qubits": n, "parameters": P, "rounds": rounds, "runs": {},
+                 "fragments": [{"n": fs.prog.n, "rows": s[0], "width": s[1], "occurrences": o,
+                                "compiled": fs.dprog.module is not None} for fs, s, o in zip(pk.frags, shapes, occs)]}
+        row_bytes = sum(s[0] * s[1] * 8 for s in shapes)
+        shifts = (np.pi / 2) * np.concatenate([np.eye(P), -np.eye(P)])  # [2P, P]
+        for B in (1, 16):
+            V = rng.uniform(-np.pi, np.pi, (B, P))
+            for M in (1, 64, 1024):
+                masks = [prng.getrandbits(n) for _ in range(M)]
+                w = rng.uniform(-1, 1, M)
+
+                def cotangent():
+                    return pk.value_and_gradient(V, masks, w)[1]
+
+                def reduce_route():
+                    return np.einsum("bmp,m->bp", pk.value_and_gradient(V, masks)[1], w)
+
+                def baseline():
+                    E = pk.expectation((V[:, None, :] + shifts[None]).reshape(-1, P), masks, w).reshape(B, 2, P)
+                    return 0.5 * (E[:, 0] - E[:, 1])
+
+                routes = {"cotangent": cotangent, "reduce": reduce_route}
+                if 2 * P * B * row_bytes <= GRADIENT_BASELINE_MAX_BYTES:
+                    routes["expectation_at_2P_shifts"] = baseline
+                got = {name: fn() for name, fn in routes.items()}
+                run = alternated(torch, routes, rounds)
+                run["max_abs_diff_to_cotangent"] = {k: float(np.abs(g - got["cotangent"]).max()) for k, g in got.items()}
+                run["reduce_over_cotangent"] = run["reduce"]["median_ms"] / run["cotangent"]["median_ms"]
+                if "expectation_at_2P_shifts" in run:
+                    run["baseline_over_cotangent"] = run["expectation_at_2P_shifts"]["median_ms"] / run["cotangent"]["median_ms"]
+                entry["runs"][f"B{B}_M{M}"] = run
+                print(label, f"B={B} M={M}", json.dumps(run), flush=True)
+        # the kernel beside the sweep, on one chunk's rows
+        f = max(range(len(shapes)), key=lambda i: shapes[i][0] * shapes[i][1])
+        fs, (rows, width) = pk.frags[f], shapes[f]
+        nel = rows * width
+        olist = fs.prog.shift_occurrences()
+        b0, b1, o0, o1 = pk.shift_chunks(16, len(olist), nel * 8, engine.GRADIENT_ROW_BYTES)[0]
+        nb, no = b1 - b0, o1 - o0
+        mats = fs.prog.bind_matrices_shifted(V[b0:b1], olist[o0:o1]).reshape(nb * no * 2, fs.prog.num_params, 2, 2)
+        Q = engine.sweep_fragment_bound(ctx, fs, mats).view(nb * no * 2, nel)
+        D = torch.randn((nb, nel), dtype=torch.float64, device="cuda")
+        out = torch.empty(nb * no * 2, dtype=torch.float64, device="cuda")
+        t_dot = timed(torch, lambda: engine.rows_dot(ctx, Q, D, 2 * no, out=out))
+        t_sweep = timed(torch, lambda: engine.sweep_fragment_bound(ctx, fs, mats), reps=5, warm=1)
+        read = (Q.numel() + D.numel()) * 8
+        entry["chunk"] = {"fragment": f, "bindings": nb, "occurrences": no, "units": nb * no * 2, "n": nel,
+                          "bytes_read": read, "qk_rows_dot": dict(t_dot, read_GBs=read / t_dot["median_ms"] / 1e6),
+                          "sweep_fragment_bound": t_sweep,
+                          "sweep_over_dot": t_sweep["median_ms"] / t_dot["median_ms"]}
+        print(label, "chunk", json.dumps(entry["chunk"]), flush=True)
+        del Q, D
+        res["cases"][label] = entry
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gradient", action="store_true", help="the parameter-shift gradient leg only (see gradient_leg)")
     ap.add_argument("--parametric", action="store_true", help="the run-time parameter leg only (see parametric_leg)")
     ap.add_argument("--projection", action="store_true",
                     help="the nearest-probability-distribution leg only (see projection_leg)")
@@ -914,6 +1026,8 @@ def main():
         return shots_child()
     if args.parametric:
         return parametric_leg(args)
+    if args.gradient:
+        return gradient_leg(args)
     if args.shots:
         return shots_leg(args)
     if args.spectrum:
